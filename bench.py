@@ -8,7 +8,8 @@
 A "step" is one UNet forward of the t2v-turbo sampling loop (timesteps cycle through the 4-step
 LCM table [999,759,519,279]) on synthetic inputs already resident in HBM.  Multi-GPU = independent
 replicas (inference shards by clip, no collective): weak scaling, value = N*K / max-over-ranks time.
-Rank 0 prints ONE JSON line (see DESIGN.md §Measurement for the extra objects).
+Rank 0 prints ONE JSON line (see DESIGN.md §Measurement for the extra objects).  `--dump-outputs DIR` writes the UNet output of
+the last timed step as DIR/unet_out.npy (float32); weights and inputs are seeded, so two builds compare output for output.
 
 `python bench.py --gpus N` without a torchrun environment re-executes itself under `torch.distributed.run`
 (one rank per GPU, rendezvous on 127.0.0.1).  At N > 1 the `distill_step` leg (BASELINE config C3) runs on
@@ -567,6 +568,16 @@ def distill_step_leg(teacher, dev, world=1, dry=False, parity=True):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path returned in its last step, as float32 .npy files.  Weights and inputs come from fixed
+    seeds, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {sorted(arrays)}")
+
+
 def self_spawn(n):
     """`python bench.py --gpus N` from a plain shell: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -597,7 +608,11 @@ def main():
     ap.add_argument("--distill-parity", type=int, default=1, help="gate the distillation leg on its gradient parity check (N = 1)")
     ap.add_argument("--full-finetune", type=int, default=1, help="also time the full fine-tuning student step (v2 script's call pattern; rank 0, N = 1)")
     ap.add_argument("--dry-run-cpu", type=int, default=0, help="plumbing check on CPU: tiny widths, gloo, emulated kernels (not a measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the UNet output of the last timed step as DIR/unet_out.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # plain `python bench.py --gpus N`: become N ranks
         sys.exit(self_spawn(args.gpus))
@@ -658,13 +673,16 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(i)
+            y = step(i)
         barrier()
         elapsed = time.perf_counter() - t0
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"unet_out": y})
+    del y
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.steps / elapsed
 

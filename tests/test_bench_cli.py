@@ -22,3 +22,28 @@ def test_bench_gpus_2_self_spawns_two_ranks_and_all_reduces():
     d = out["distill_step"]
     assert d["n_gpus"] == 2 and d["finite"] and d["allreduce_ms"] > 0 and "gloo" in d["grad_exchange"]
     assert abs(d["samples_per_s"] - 2e3 / d["ms_per_step"]) < 1e-2 * d["samples_per_s"] + 1e-3   # global = ranks x per-rank
+
+
+def test_bench_steps_and_dump_outputs_are_reproducible(tmp_path):
+    """`--steps K` sets the number of timed steps reported in the line next to `ms_per_step`, and `--dump-outputs DIR` writes the
+    last timed step's UNet output as float32; two runs with the same arguments dump the same array (seeded weights and inputs)."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run-cpu", "1", "--distill", "0",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+        assert sorted(p.name for p in d.iterdir()) == ["unet_out.npy"]
+        y = np.load(d / "unet_out.npy")
+        assert y.dtype == np.float32 and y.shape == (1, 4, 2, 8, 8) and np.isfinite(y).all() and np.abs(y).max() > 0
+        dumps.append(y)
+    assert np.array_equal(dumps[0], dumps[1])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-cpu", "1", "--steps", "0"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
