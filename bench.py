@@ -8,11 +8,17 @@
 A "step" is one UNet forward of the t2v-turbo sampling loop (timesteps cycle through the 4-step
 LCM table [999,759,519,279]) on synthetic inputs already resident in HBM.  Multi-GPU = independent
 replicas (inference shards by clip, no collective): weak scaling, value = N*K / max-over-ranks time.
-Rank 0 prints ONE JSON line (see DESIGN.md §Measurement for the extra objects).  `--dump-outputs DIR` writes the UNet output of
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` writes the UNet output of
 the last timed step as DIR/unet_out.npy (float32); weights and inputs are seeded, so two builds compare output for output.
 
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump, print.  `--full` adds the
+legs that take runs of their own (see DESIGN.md §Measurement for their objects): the per-kernel breakdown and the in-graph
+roofline, the 4-step and 16-step v2 clips with VAE decode, the CPU oracle baseline with its parity gate, the distillation
+step with its parity gate and the full fine-tuning step.  `--breakdown`, `--clip`, `--cpu-baseline`, `--distill` and
+`--full-finetune` switch one leg on or off either way.
+
 `python bench.py --gpus N` without a torchrun environment re-executes itself under `torch.distributed.run`
-(one rank per GPU, rendezvous on 127.0.0.1).  At N > 1 the `distill_step` leg (BASELINE config C3) runs on
+(one rank per GPU, rendezvous on 127.0.0.1).  With `--full` at N > 1 the `distill_step` leg (BASELINE config C3) runs on
 every rank with the real flat-buffer gradient all-reduce (RCCL) and reports global samples/s.
 `--dry-run-cpu 1` runs the same control flow on CPU (tiny widths, gloo, the emulated op backend of the test
 suite): a plumbing check of the multi-rank path for boxes without GPUs, labelled as such, never a measurement.
@@ -600,19 +606,26 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", type=int, default=1, help="replay the recorded forward as one hipGraph")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg below whose switch is not given: breakdown, clips, CPU baseline, distillation, full fine-tuning")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="time the CPU oracle and gate on its parity (N = 1; default: --full)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU sample (0 = the whole 16-frame clip)")
-    ap.add_argument("--clip", type=int, default=1, help="also time the 4-step clip and the 16-step v2 clip incl. VAE decode")
-    ap.add_argument("--breakdown", type=int, default=1)
-    ap.add_argument("--distill", type=int, default=1, help="also time the v1 distillation step (config C3; on every rank at N > 1)")
+    ap.add_argument("--clip", type=int, default=None, help="also time the 4-step clip and the 16-step v2 clip incl. VAE decode (default: --full)")
+    ap.add_argument("--breakdown", type=int, default=None, help="per-kernel times and the GEMM-family roofline (default: --full)")
+    ap.add_argument("--distill", type=int, default=None,
+                    help="also time the v1 distillation step (config C3; on every rank at N > 1; default: --full)")
     ap.add_argument("--distill-parity", type=int, default=1, help="gate the distillation leg on its gradient parity check (N = 1)")
-    ap.add_argument("--full-finetune", type=int, default=1, help="also time the full fine-tuning student step (v2 script's call pattern; rank 0, N = 1)")
+    ap.add_argument("--full-finetune", type=int, default=None,
+                    help="also time the full fine-tuning student step (v2 script's call pattern; rank 0, N = 1; default: --full)")
     ap.add_argument("--dry-run-cpu", type=int, default=0, help="plumbing check on CPU: tiny widths, gloo, emulated kernels (not a measurement)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the UNet output of the last timed step as DIR/unet_out.npy (float32)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for leg in ("breakdown", "clip", "cpu_baseline", "distill", "full_finetune"):
+        if getattr(args, leg) is None:
+            setattr(args, leg, int(args.full))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # plain `python bench.py --gpus N`: become N ranks
         sys.exit(self_spawn(args.gpus))
