@@ -434,6 +434,45 @@ int t2v_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
 int t2v_ema_update(float* target, const float* src, float rate, long long n, void* stream);
 int t2v_sumsq(const float* x, long long n, float* ws, float* out, void* stream);
 
+/* ---------------------------------------------------------------- block-wise 8-bit AdamW (optim.AdamW8bit; Dettmers et al. 2021)
+ * The two moments of every parameter tensor are stored as one byte per element — an index into a 256-entry fp32 code book of values
+ * in [-1, 1] (first moment) / [0, 1] (second moment) — plus one fp32 absmax per QUANTISATION BLOCK of 256 consecutive elements of
+ * ONE tensor: value = code[byte] * absmax[block].  Each tensor's state is padded up to whole blocks (no block straddles two
+ * tensors); the padding bytes of a last, partial block hold the code of 0 and take no part in the block's absmax.
+ *
+ * t2v_adamw8_step updates MANY tensors in one launch.  `table` is a DEVICE array of n_tensors descriptors, one per tensor that
+ * has a gradient this step, ordered by work0: the launch covers work blocks [0, n_blocks), tensor i owning
+ * [work0, work0 + ceil(n / 256)).  Parameters and gradients are contiguous fp32 anywhere in memory; a tensor whose param or grad
+ * pointer is not 16-byte aligned is read and written with scalar accesses (chosen in the kernel: views into gradient buckets may
+ * be 4-byte aligned), the arenas must be 16-byte aligned.  Flag T2V_ADAMW8_F32_STATE: the tensor keeps fp32 moments (small
+ * tensors), at state_block * 256 floats into state1_f32 / state2_f32; otherwise its codes are at state_block * 256 bytes into
+ * state1 / state2 and its absmax at absmax1 / absmax2 [state_block ...].  An arena that no tensor of the table uses may be NULL.
+ * Arithmetic: torch.optim.AdamW (decoupled decay, bias correction by `step`), in the operation order of t2v_adamw_step; the
+ * parameter is updated from the fresh fp32 moments, which are then re-quantised to the nearest code (ties to the lower code).
+ * code1 / code2: 256 strictly increasing floats each.
+ * t2v_quant8_blockwise / t2v_dequant8_blockwise: fp32 <-> codes (ceil(n / 256) * 256 bytes) + absmax (ceil(n / 256) floats). */
+#define T2V_ADAMW8_BLOCK 256
+#define T2V_ADAMW8_F32_STATE 1
+typedef struct t2v_adamw8_tensor {
+    float* param;
+    const float* grad;
+    long long state_block; /* first block of this tensor's state in the 8-bit (or, with F32_STATE, the fp32) arenas */
+    long long n;           /* elements */
+    long long work0;       /* first work block of this tensor in this launch */
+    float lr;
+    float weight_decay;
+    int flags;
+    int reserved;
+} t2v_adamw8_tensor;
+int t2v_adamw8_step(const t2v_adamw8_tensor* table, int n_tensors, long long n_blocks, unsigned char* state1,
+                    unsigned char* state2, float* absmax1, float* absmax2, float* state1_f32, float* state2_f32,
+                    const float* code1, const float* code2, float beta1, float beta2, float eps, int step,
+                    float grad_scale, void* stream);
+int t2v_quant8_blockwise(const float* x, long long n, const float* code, unsigned char* codes, float* absmax,
+                         void* stream);
+int t2v_dequant8_blockwise(const unsigned char* codes, const float* absmax, const float* code, float* out, long long n,
+                           void* stream);
+
 /* ---------------------------------------------------------------- LoRA training path (utils/lora.py:45-50,124-129,204-209)
  * t2v_gather_f32: indexed re-layout of fp32 data.  accumulate = 0: out[i] = idx[i] >= 0 ? alpha*src[idx[i]] : 0;
  * accumulate = 1: out[i] += alpha*src[idx[i]] where idx[i] >= 0.  out is fp32 (T2V_F32) or bf16 (T2V_BF16).

@@ -10,7 +10,11 @@ in ``_ALIASES`` (the modules on the hot path); every other module of the referen
 importing from the checkout on ``sys.path`` exactly as before (predict.py:12-15,
 train_t2v_turbo_v1_lora.py:46-69).  A parent package (``lvdm``, ``utils`` ...) is synthesised only
 when nothing else on the path provides it, so the aliases also work without a checkout.
-``install()`` refuses to shadow an already imported reference module unless ``force=True``."""
+``install()`` refuses to shadow an already imported reference module unless ``force=True``.
+
+``import bitsandbytes as bnb; bnb.optim.AdamW8bit`` — what ``--use_8bit_adam`` makes the trainers do
+(train_t2v_turbo_v1_lora.py:765-773, train_latent_t2v_turbo_v2.py:787-795) — is answered as well, with ``optim.AdamW8bit``, but
+only when no real ``bitsandbytes`` can be imported (the real package wins, as for the parents)."""
 import importlib
 import importlib.abc
 import importlib.machinery
@@ -38,6 +42,11 @@ _ALIASES = {
                             "extract_lora_ups_down", "save_lora_weight", "collapse_lora", "monkeypatch_remove_lora"]),
     "utils.lora_handler": ("lora", ["LoraHandler"]),
 }
+# stand-in modules for a package that has no ROCm build: served only while the real one is not importable
+_FALLBACKS = {
+    "bitsandbytes": {"optim": "module:bitsandbytes.optim"},
+    "bitsandbytes.optim": {"AdamW8bit": "optim:AdamW8bit", "AdamW": "torch.optim:AdamW"},
+}
 # packages that sit above an alias: taken from the checkout when it has them, synthesised otherwise
 _PARENTS = {".".join(d.split(".")[:i]) for d in _ALIASES for i in range(1, len(d.split(".")))}
 
@@ -45,9 +54,16 @@ _PARENTS = {".".join(d.split(".")[:i]) for d in _ALIASES for i in range(1, len(d
 class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
     __t2v_amd_alias__ = True
 
+    def _real(self, name, path=None, target=None):
+        return any(f is not self and hasattr(f, "find_spec") and f.find_spec(name, path, target) is not None for f in sys.meta_path)
+
     def find_spec(self, name, path=None, target=None):
         if name in _ALIASES:
             return importlib.machinery.ModuleSpec(name, self, is_package=name in _PARENTS)
+        if name in _FALLBACKS:
+            if self._real(name.split(".")[0]):
+                return None
+            return importlib.machinery.ModuleSpec(name, self, is_package="." not in name)
         if name in _PARENTS:
             for finder in sys.meta_path:  # the real package wins: its other submodules must stay importable
                 if finder is self or not hasattr(finder, "find_spec"):
@@ -62,6 +78,16 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
     def exec_module(self, module):
         module.__t2v_amd_alias__ = True
+        if module.__name__ in _FALLBACKS:
+            if "." not in module.__name__:
+                module.__path__ = []
+            for n, where in _FALLBACKS[module.__name__].items():
+                src, attr = where.split(":")
+                if src == "module":
+                    setattr(module, n, importlib.import_module(attr))
+                else:
+                    setattr(module, n, getattr(importlib.import_module(src if "." in src else f"t2v_turbo_amd.{src}"), attr))
+            return
         if module.__name__ not in _ALIASES:  # synthesised parent
             module.__path__ = []
             return

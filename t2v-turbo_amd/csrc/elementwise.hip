@@ -443,6 +443,200 @@ extern "C" int t2v_sumsq(const float* x, long long n, float* ws, float* out, voi
     return T2V_OK;
 }
 
+// ---- block-wise 8-bit AdamW (optim.AdamW8bit) ----------------------------------------------------------
+// One WAVE per quantisation block of 256 elements, 4 per lane: a 16-byte load each of the parameter and the gradient, one dword each
+// of the two code arrays.  Both code books and the midpoints between neighbouring codes live in LDS (4 KiB, loaded once per
+// workgroup: the grid is persistent); the nearest code of a value is the number of midpoints below it, an 8-step binary search.
+// The two absmax reductions are wave shuffles: no workgroup barrier inside the loop.  Bandwidth: 16 B per element (fp32 moments: 28).
+// Floating-point contraction is OFF in these kernels: the moments decide the stored absmax and codes, which optim.py's CPU
+// restatement (separately rounded multiplies and adds) reproduces bit for bit only without fused multiply-adds.
+namespace {
+struct Book8 {
+    float code[256];
+    float mid[256];   // mid[i] = (code[i] + code[i + 1]) / 2, i < 255
+};
+__device__ __forceinline__ void book8_load(Book8& b, const float* code, int tid) {   // 256 threads
+    const float c = code[tid];
+    b.code[tid] = c;
+    b.mid[tid] = tid < 255 ? 0.5f * (c + code[tid + 1]) : 3.0e38f;
+}
+__device__ __forceinline__ unsigned book8_nearest(const Book8& b, float x) {   // NaN -> 0; always in [0, 255]
+    unsigned idx = 0;
+#pragma unroll
+    for (unsigned s = 128; s > 0; s >>= 1) idx += (b.mid[idx + s - 1] < x) ? s : 0u;
+    return idx;
+}
+__device__ __forceinline__ uint32_t book8_quant4(const Book8& b, const float* v, float absmax) {
+#pragma clang fp contract(off)
+    uint32_t q = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q |= book8_nearest(b, absmax > 0.f ? v[j] / absmax : 0.f) << (8 * j);
+    return q;
+}
+// the 4 elements of this lane: how many are inside the tensor, and whether they can move as one 16-byte access
+__device__ __forceinline__ int lane_count4(long long n, long long e0) {
+    const long long rem = n - e0;
+    return rem >= 4 ? 4 : rem > 0 ? (int)rem : 0;
+}
+__device__ __forceinline__ void load4(const float* base, long long e0, int k, bool vec, float* out) {
+    if (k == 4 && vec) {
+        const float4 t = *(const float4*)(base + e0);
+        out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = j < k ? base[e0 + j] : 0.f;
+    }
+}
+__device__ __forceinline__ void store4(float* base, long long e0, int k, bool vec, const float* v) {
+    if (k == 4 && vec) {
+        *(float4*)(base + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < k) base[e0 + j] = v[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw8_kernel(const t2v_adamw8_tensor* table, int nt, long long nblocks, uint32_t* s1,
+                                                     uint32_t* s2, float* am1, float* am2, float* f1, float* f2,
+                                                     const float* code1, const float* code2, float b1, float b2, float eps,
+                                                     float bc1, float bc2_sqrt, float gscale) {
+#pragma clang fp contract(off)
+    __shared__ Book8 book[2];
+    book8_load(book[0], code1, threadIdx.x);
+    book8_load(book[1], code2, threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (long long blk = (long long)blockIdx.x * 4 + wave; blk < nblocks; blk += (long long)gridDim.x * 4) {
+        int lo = 0, hi = nt - 1;   // the tensor that owns this work block: the last one with work0 <= blk (wave-uniform)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[mid].work0 <= blk) lo = mid; else hi = mid - 1;
+        }
+        const t2v_adamw8_tensor d = table[lo];
+        const long long local = blk - d.work0;
+        const long long e0 = local * T2V_ADAMW8_BLOCK + lane * 4;
+        const int k = lane_count4(d.n, e0);   // 0 for the padding lanes of a last, partial block: they touch no parameter data
+        const bool vec = (((uintptr_t)d.param | (uintptr_t)d.grad) & 15) == 0;
+        const long long sb = d.state_block + local;
+        const bool f32_state = (d.flags & T2V_ADAMW8_F32_STATE) != 0;
+        float P[4], G[4], M[4], V[4];
+        load4(d.param, e0, k, vec, P);
+        load4(d.grad, e0, k, vec, G);
+        if (f32_state) {
+            load4(f1, sb * T2V_ADAMW8_BLOCK + lane * 4, 4, true, M);
+            load4(f2, sb * T2V_ADAMW8_BLOCK + lane * 4, 4, true, V);
+        } else {
+            const uint32_t c1 = s1[sb * 64 + lane], c2 = s2[sb * 64 + lane];
+            const float a1 = am1[sb], a2 = am2[sb];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                M[j] = book[0].code[(c1 >> (8 * j)) & 255u] * a1;
+                V[j] = book[1].code[(c2 >> (8 * j)) & 255u] * a2;
+            }
+        }
+        const float decay = 1.0f - d.lr * d.weight_decay, step_size = d.lr / bc1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < k) {   // t2v_adamw_step's order of operations
+                const float gr = G[j] * gscale;
+                P[j] *= decay;
+                M[j] = b1 * M[j] + (1.0f - b1) * gr;
+                V[j] = b2 * V[j] + (1.0f - b2) * gr * gr;
+                P[j] -= step_size * M[j] / (sqrtf(V[j]) / bc2_sqrt + eps);
+            } else {
+                M[j] = 0.f; V[j] = 0.f;
+            }
+        }
+        store4(d.param, e0, k, vec, P);   // from the fresh fp32 moments, not the re-quantised ones
+        if (f32_state) {
+            store4(f1, sb * T2V_ADAMW8_BLOCK + lane * 4, 4, true, M);
+            store4(f2, sb * T2V_ADAMW8_BLOCK + lane * 4, 4, true, V);
+        } else {
+            const float mx1 = wave_max(fmaxf(fmaxf(fabsf(M[0]), fabsf(M[1])), fmaxf(fabsf(M[2]), fabsf(M[3]))));
+            const float mx2 = wave_max(fmaxf(fmaxf(fabsf(V[0]), fabsf(V[1])), fmaxf(fabsf(V[2]), fabsf(V[3]))));
+            s1[sb * 64 + lane] = book8_quant4(book[0], M, mx1);
+            s2[sb * 64 + lane] = book8_quant4(book[1], V, mx2);
+            if (lane == 0) { am1[sb] = mx1; am2[sb] = mx2; }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void quant8_kernel(const float* x, long long n, long long nblocks, const float* code, uint32_t* codes,
+                                                     float* absmax) {
+    __shared__ Book8 book;
+    book8_load(book, code, threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool vec = ((uintptr_t)x & 15) == 0;
+    for (long long blk = (long long)blockIdx.x * 4 + wave; blk < nblocks; blk += (long long)gridDim.x * 4) {
+        const long long e0 = blk * T2V_ADAMW8_BLOCK + lane * 4;
+        float X[4];
+        load4(x, e0, lane_count4(n, e0), vec, X);   // padding lanes: 0
+        const float mx = wave_max(fmaxf(fmaxf(fabsf(X[0]), fabsf(X[1])), fmaxf(fabsf(X[2]), fabsf(X[3]))));
+        codes[blk * 64 + lane] = book8_quant4(book, X, mx);
+        if (lane == 0) absmax[blk] = mx;
+    }
+}
+__global__ __launch_bounds__(256) void dequant8_kernel(const uint32_t* codes, const float* absmax, const float* code, float* out,
+                                                       long long n, long long nblocks) {
+    __shared__ Book8 book;
+    book8_load(book, code, threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool vec = ((uintptr_t)out & 15) == 0;
+    for (long long blk = (long long)blockIdx.x * 4 + wave; blk < nblocks; blk += (long long)gridDim.x * 4) {
+        const long long e0 = blk * T2V_ADAMW8_BLOCK + lane * 4;
+        const uint32_t c = codes[blk * 64 + lane];
+        const float a = absmax[blk];
+        float X[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) X[j] = book.code[(c >> (8 * j)) & 255u] * a;
+        store4(out, e0, lane_count4(n, e0), vec, X);
+    }
+}
+// persistent grid: 8 workgroups of 4 waves per CU of a 256-CU part fill every wave slot; fewer when there is less work
+inline unsigned blocks8(long long nblocks) { return (unsigned)((nblocks + 3) / 4 < 2048 ? (nblocks + 3) / 4 : 2048); }
+}  // namespace
+
+extern "C" int t2v_adamw8_step(const t2v_adamw8_tensor* table, int n_tensors, long long n_blocks, unsigned char* state1,
+                               unsigned char* state2, float* absmax1, float* absmax2, float* state1_f32, float* state2_f32,
+                               const float* code1, const float* code2, float beta1, float beta2, float eps, int step,
+                               float grad_scale, void* stream) {
+    T2V_REQUIRE(table && code1 && code2 && n_tensors > 0 && n_blocks >= n_tensors && step >= 1, T2V_EINVAL, "t2v_adamw8_step");
+    T2V_REQUIRE((state1 && state2 && absmax1 && absmax2) || (state1_f32 && state2_f32), T2V_EINVAL, "t2v_adamw8_step: no state arena");
+    T2V_REQUIRE(!state1 == !state2 && !state1 == !absmax1 && !state1 == !absmax2 && !state1_f32 == !state2_f32, T2V_EINVAL,
+                "t2v_adamw8_step: an arena is given for one moment only");
+    T2V_REQUIRE(((uintptr_t)state1 | (uintptr_t)state2 | (uintptr_t)state1_f32 | (uintptr_t)state2_f32) % 16 == 0 && (uintptr_t)table % 8 == 0,
+                T2V_ESHAPE, "t2v_adamw8_step: the state arenas must be 16-byte aligned (the table 8-byte)");
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adamw8_kernel, dim3(blocks8(n_blocks)), dim3(256), 0, (hipStream_t)stream, table, n_tensors, n_blocks,
+                       (uint32_t*)state1, (uint32_t*)state2, absmax1, absmax2, state1_f32, state2_f32, code1, code2, beta1, beta2,
+                       eps, bc1, sqrtf(bc2), grad_scale);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+extern "C" int t2v_quant8_blockwise(const float* x, long long n, const float* code, unsigned char* codes, float* absmax,
+                                    void* stream) {
+    T2V_REQUIRE(x && code && codes && absmax && n > 0, T2V_EINVAL, "t2v_quant8_blockwise");
+    T2V_REQUIRE((uintptr_t)codes % 4 == 0, T2V_ESHAPE, "t2v_quant8_blockwise: codes must be 4-byte aligned");
+    const long long nblocks = (n + T2V_ADAMW8_BLOCK - 1) / T2V_ADAMW8_BLOCK;
+    hipLaunchKernelGGL(quant8_kernel, dim3(blocks8(nblocks)), dim3(256), 0, (hipStream_t)stream, x, n, nblocks, code,
+                       (uint32_t*)codes, absmax);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+extern "C" int t2v_dequant8_blockwise(const unsigned char* codes, const float* absmax, const float* code, float* out, long long n,
+                                      void* stream) {
+    T2V_REQUIRE(codes && absmax && code && out && n > 0, T2V_EINVAL, "t2v_dequant8_blockwise");
+    T2V_REQUIRE((uintptr_t)codes % 4 == 0, T2V_ESHAPE, "t2v_dequant8_blockwise: codes must be 4-byte aligned");
+    const long long nblocks = (n + T2V_ADAMW8_BLOCK - 1) / T2V_ADAMW8_BLOCK;
+    hipLaunchKernelGGL(dequant8_kernel, dim3(blocks8(nblocks)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)codes, absmax,
+                       code, out, n, nblocks);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
 // ---- library state ---------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
 void t2v_set_error(const char* msg) {

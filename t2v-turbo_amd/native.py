@@ -29,6 +29,16 @@ class WgradProblem(C.Structure):
                 ("ldo", C.c_int), ("R", C.c_int), ("C", C.c_int), ("alpha", C.c_float)]
 
 
+ADAMW8_BLOCK = 256       # T2V_ADAMW8_BLOCK
+ADAMW8_F32_STATE = 1     # T2V_ADAMW8_F32_STATE
+
+
+class Adamw8Tensor(C.Structure):
+    """struct t2v_adamw8_tensor, field for field (56 bytes)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state_block", C.c_longlong), ("n", C.c_longlong),
+                ("work0", C.c_longlong), ("lr", C.c_float), ("weight_decay", C.c_float), ("flags", C.c_int), ("reserved", C.c_int)]
+
+
 class GemmDesc(C.Structure):
     """struct t2v_gemm_desc"""
     _fields_ = [
@@ -223,6 +233,11 @@ _SIGS = {
                                  C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]),
     "t2v_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_longlong, C.c_void_p]),
     "t2v_sumsq": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2v_adamw8_step": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
+                                  C.c_void_p]),
+    "t2v_quant8_blockwise": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2v_dequant8_blockwise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "t2v_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
     "t2v_attn_spatial_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
@@ -816,6 +831,27 @@ class HipOps:
     def adamw_step(self, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
         self._call("t2v_adamw_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2,
                    eps, weight_decay, step, grad_scale)
+
+    def adamw8_step(self, table, n_tensors, n_blocks, state1, state2, absmax1, absmax2, state1_f32, state2_f32, code1, code2,
+                    beta1, beta2, eps, step, grad_scale=1.0):
+        """Block-wise 8-bit AdamW over every tensor of ``table`` (a uint8 device tensor holding ``n_tensors`` ``Adamw8Tensor``
+        records) in one launch; an arena nobody uses may be None (include/t2v_hip.h)."""
+        assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(Adamw8Tensor)
+        self._call("t2v_adamw8_step", _p(table), n_tensors, n_blocks, _p(state1), _p(state2), _p(absmax1), _p(absmax2),
+                   _p(state1_f32), _p(state2_f32), _p(code1), _p(code2), beta1, beta2, eps, step, grad_scale)
+
+    def quant8(self, x, code, codes, absmax):
+        """fp32 ``x`` -> one code per element (uint8, padded to whole 256-element blocks) + one fp32 absmax per block."""
+        nb = (x.numel() + ADAMW8_BLOCK - 1) // ADAMW8_BLOCK
+        assert x.dtype == torch.float32 and x.is_contiguous() and codes.dtype == torch.uint8 and codes.numel() >= nb * ADAMW8_BLOCK
+        assert absmax.dtype == torch.float32 and absmax.numel() >= nb and code.dtype == torch.float32 and code.numel() == 256
+        self._call("t2v_quant8_blockwise", _p(x), x.numel(), _p(code), _p(codes), _p(absmax))
+
+    def dequant8(self, codes, absmax, code, out):
+        nb = (out.numel() + ADAMW8_BLOCK - 1) // ADAMW8_BLOCK
+        assert out.dtype == torch.float32 and out.is_contiguous() and codes.dtype == torch.uint8 and codes.numel() >= nb * ADAMW8_BLOCK
+        assert absmax.dtype == torch.float32 and absmax.numel() >= nb and code.dtype == torch.float32 and code.numel() == 256
+        self._call("t2v_dequant8_blockwise", _p(codes), _p(absmax), _p(code), _p(out), out.numel())
 
     def ema_update(self, target, src, rate):
         self._call("t2v_ema_update", _p(target), _p(src), rate, target.numel())

@@ -2,7 +2,12 @@
 (``dist.FlatGradSync``) and the optimizer moments each live in ONE contiguous fp32 buffer, so an optimizer
 step is one fused HIP kernel (``t2v_adamw_step``) instead of bitsandbytes' CUDA-only 8-bit AdamW
 (train_t2v_turbo_v1_lora.py:765-803) or 1150 small torch launches; the clip coefficient of
-``clip_grad_norm_`` (:1193) is folded into the same pass.  On CPU tensors the same arithmetic runs in torch."""
+``clip_grad_norm_`` (:1193) is folded into the same pass.  On CPU tensors the same arithmetic runs in torch.
+
+``AdamW8bit`` (below ``FlatAdamW``) is the ``torch.optim.Optimizer`` the reference's ``--use_8bit_adam`` asks for
+(``bnb.optim.AdamW8bit``): parameters and gradients stay where the trainer put them, the two moments are stored block-wise in
+8 bits (``t2v_adamw8_step``, one launch for every tensor).  ``compat.install()`` serves it as ``bitsandbytes.optim.AdamW8bit``."""
+import numpy as np
 import torch
 
 
@@ -100,3 +105,315 @@ def update_ema_flat(target_flat, source_flat, rate=0.99, target_params=None):
         target_flat.mul_(rate).add_(source_flat, alpha=1 - rate)
     if target_params:
         target_params[0].add_(0.0)
+
+
+# ------------------------------------------------------------------------------------------------ block-wise 8-bit AdamW
+QBLOCK = 256   # elements per quantisation block (T2V_ADAMW8_BLOCK)
+
+
+def _dynamic_levels(top, decades):
+    """Values in (0, 1), denser toward 0: decade d = 0, 1, ... covers [10^-(d+1), 10^-d] with ``top >> d`` evenly spaced values
+    (the centres of that many equal cells) — a decade exponent and a linear fraction whose resolution halves per decade, the
+    'dynamic' data type of Dettmers et al. 2021."""
+    out = []
+    for d in range(decades):
+        k = top >> d
+        edges = np.linspace(0.1, 1.0, k + 1)
+        out += list(0.5 * (edges[:-1] + edges[1:]) * 10.0 ** -d)
+    return out
+
+
+def make_code_books():
+    """(signed, unsigned): two tables of 256 strictly increasing fp32 values.  Signed (first moment): -1, 126 negative levels over
+    6 decades, 0, 127 positive levels over 7 decades, 1.  Unsigned (second moment): 0, 254 levels over 7 decades, 1.  These are this
+    project's OWN tables: they follow the published layout, not bitsandbytes' arrays, which are not available to compare with."""
+    signed = [-1.0] + [-x for x in _dynamic_levels(64, 6)] + [0.0] + _dynamic_levels(64, 7) + [1.0]
+    unsigned = [0.0] + _dynamic_levels(128, 7) + [1.0]
+    books = []
+    for vals in (signed, unsigned):
+        t = torch.tensor(sorted(vals), dtype=torch.float64).to(torch.float32)
+        assert t.numel() == 256 and bool((t[1:] > t[:-1]).all())
+        books.append(t)
+    return books[0], books[1]
+
+
+def _midpoints(code):
+    return (code[:-1] + code[1:]) * 0.5   # fp32, as the kernel forms them
+
+
+def quantize_blockwise(x, code):
+    """fp32 tensor -> (codes uint8 [ceil(n / 256) * 256], absmax fp32 [ceil(n / 256)]): per block of 256 consecutive elements,
+    absmax = max |x| and code = index of the table value nearest to x / absmax (a value exactly between two codes takes the
+    lower one; an all-zero block has absmax 0 and the code of 0).  The padding of a last, partial block holds the code of 0."""
+    x = x.detach().reshape(-1).float()
+    n = x.numel()
+    nb = (n + QBLOCK - 1) // QBLOCK
+    if x.is_cuda:
+        codes = torch.empty(nb * QBLOCK, dtype=torch.uint8, device=x.device)
+        absmax = torch.empty(nb, dtype=torch.float32, device=x.device)
+        _shared_ops().quant8(x.contiguous(), code.to(x.device), codes, absmax)
+        return codes, absmax
+    xp = torch.zeros(nb * QBLOCK, dtype=torch.float32)
+    xp[:n] = x
+    xp = xp.view(nb, QBLOCK)
+    absmax = xp.abs().amax(dim=1)
+    xn = torch.where(absmax[:, None] > 0, xp / absmax[:, None], torch.zeros_like(xp))
+    codes = torch.bucketize(xn, _midpoints(code))   # number of midpoints strictly below the value
+    return codes.to(torch.uint8).reshape(-1), absmax
+
+
+def dequantize_blockwise(codes, absmax, code, n):
+    """The inverse map: value = code[byte] * absmax[block], the first ``n`` elements."""
+    if codes.is_cuda:
+        out = torch.empty(n, dtype=torch.float32, device=codes.device)
+        _shared_ops().dequant8(codes, absmax, code.to(codes.device), out)
+        return out
+    nb = (n + QBLOCK - 1) // QBLOCK
+    return (code[codes[:nb * QBLOCK].long()].view(nb, QBLOCK) * absmax[:nb, None]).reshape(-1)[:n]
+
+
+_TABLE_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state_block", "<i8"), ("n", "<i8"), ("work0", "<i8"),
+                         ("lr", "<f4"), ("weight_decay", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])   # struct t2v_adamw8_tensor
+
+
+class AdamW8bit(torch.optim.Optimizer):
+    """AdamW (``torch.optim.AdamW`` semantics: decoupled decay, bias correction) whose two moments are stored in 8 bits, block-wise:
+    one byte per element indexing a 256-entry code book, one fp32 absmax per 256 consecutive elements of a tensor (Dettmers et
+    al. 2021).  Constructor surface of ``bitsandbytes.optim.AdamW8bit`` as far as the reference's trainers use it
+    (train_latent_t2v_turbo_v2.py:833-845: two groups, the second with its own ``lr``).  Tensors with fewer than
+    ``min_8bit_size`` elements keep fp32 moments.  Parameters and gradients are not moved: on the GPU one ``t2v_adamw8_step``
+    launch walks a device table of every tensor that has a gradient (one launch per distinct ``(betas, eps, step)`` among them);
+    on CPU tensors the same arithmetic runs in torch, block for block.
+
+    The code books are this project's own (``make_code_books``).  bitsandbytes is CUDA-only and was not available to compare
+    with: neither its tables nor its saved optimizer state are bit-compatible with this class, and no such claim is made.
+    ``load_state_dict`` takes this class's own state or a ``torch.optim.AdamW`` state (whose fp32 moments it quantises).
+    Not implemented (``NotImplementedError`` when asked for): paged state, percentile clipping, ``block_wise=False``, amsgrad."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, optim_bits=32, args=None,
+                 min_8bit_size=4096, percentile_clipping=100, block_wise=True, is_paged=False):
+        if amsgrad or optim_bits != 32 or args is not None or percentile_clipping != 100 or not block_wise or is_paged:
+            raise NotImplementedError("AdamW8bit: amsgrad / optim_bits / args / percentile_clipping / block_wise=False / is_paged "
+                                      "are accepted at their bitsandbytes defaults only")
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("AdamW8bit: invalid lr / betas / eps / weight_decay")
+        self.min_8bit_size = int(min_8bit_size)
+        self.code1, self.code2 = make_code_books()
+        self._zero1, self._zero2 = int((self.code1 == 0).nonzero()), int((self.code2 == 0).nonzero())
+        self._layout = {}            # parameter -> (8-bit?, first block in its arena, blocks)
+        self._arena = None           # dict: s1, s2 (uint8), a1, a2 (fp32 absmax), f1, f2 (fp32 moments of the small tensors)
+        self._books = {}             # device -> (code1, code2) there
+        self._table = None           # cached descriptor table of the device path
+        self.native_ops = None       # a HipOps to run the kernel with; None: the process-wide one for GPU tensors, torch on CPU tensors
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    # -- state arenas ------------------------------------------------------------------------------------------------------
+    def _all_params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _ensure_state(self):
+        """Give every parameter its slice of the arenas (append-only: a parameter group added later keeps the others' offsets)."""
+        new = [p for p in self._all_params() if p not in self._layout]
+        if not new:
+            return
+        dev = self._all_params()[0].device
+        used8 = sum(nb for is8, _, nb in self._layout.values() if is8)
+        used32 = sum(nb for is8, _, nb in self._layout.values() if not is8)
+        for p in new:
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous() or p.is_sparse:
+                raise ValueError("AdamW8bit: parameters must be dense contiguous fp32 tensors on one device")
+            nb = (p.numel() + QBLOCK - 1) // QBLOCK
+            is8 = p.numel() >= self.min_8bit_size
+            self._layout[p] = (is8, used8 if is8 else used32, nb)
+            used8, used32 = used8 + (nb if is8 else 0), used32 + (0 if is8 else nb)
+        old = self._arena
+        a = dict(s1=torch.full((used8 * QBLOCK,), self._zero1, dtype=torch.uint8, device=dev),
+                 s2=torch.full((used8 * QBLOCK,), self._zero2, dtype=torch.uint8, device=dev),
+                 a1=torch.zeros(used8, device=dev), a2=torch.zeros(used8, device=dev),
+                 f1=torch.zeros(used32 * QBLOCK, device=dev), f2=torch.zeros(used32 * QBLOCK, device=dev))
+        if old is not None:
+            for k in a:
+                a[k][:old[k].numel()].copy_(old[k])
+        self._arena, self._table = a, None
+        for p, (is8, b0, nb) in self._layout.items():   # the per-parameter state: views of the arenas
+            st = self.state[p]
+            st.setdefault("step", 0)
+            if is8:
+                st["state1"], st["state2"] = a["s1"][b0 * QBLOCK:(b0 + nb) * QBLOCK], a["s2"][b0 * QBLOCK:(b0 + nb) * QBLOCK]
+                st["absmax1"], st["absmax2"] = a["a1"][b0:b0 + nb], a["a2"][b0:b0 + nb]
+            else:
+                st["state1"] = a["f1"][b0 * QBLOCK:b0 * QBLOCK + p.numel()]
+                st["state2"] = a["f2"][b0 * QBLOCK:b0 * QBLOCK + p.numel()]
+
+    def _codes_on(self, dev):
+        if dev not in self._books:
+            self._books[dev] = (self.code1.to(dev), self.code2.to(dev))
+        return self._books[dev]
+
+    def state_bytes(self):
+        """Bytes of optimizer state (codes + absmax + the fp32 moments of the small tensors)."""
+        self._ensure_state()
+        return sum(t.numel() * t.element_size() for t in self._arena.values())
+
+    def moments(self, p):
+        """The two moments of one parameter as fp32 tensors (dequantised copies)."""
+        self._ensure_state()
+        st, (is8, _, _) = self.state[p], self._layout[p]
+        if not is8:
+            return st["state1"].clone().view_as(p), st["state2"].clone().view_as(p)
+        c1, c2 = self._codes_on(p.device)
+        return (dequantize_blockwise(st["state1"], st["absmax1"], c1, p.numel()).view_as(p),
+                dequantize_blockwise(st["state2"], st["absmax2"], c2, p.numel()).view_as(p))
+
+    def set_moments(self, p, exp_avg, exp_avg_sq, step=None):
+        """Overwrite one parameter's moments from fp32 tensors (quantised here unless the parameter keeps fp32 state)."""
+        self._ensure_state()
+        st, (is8, _, _) = self.state[p], self._layout[p]
+        if step is not None:
+            st["step"] = int(step)
+        m, v = exp_avg.detach().to(p.device, torch.float32).reshape(-1), exp_avg_sq.detach().to(p.device, torch.float32).reshape(-1)
+        if not is8:
+            st["state1"].copy_(m)
+            st["state2"].copy_(v)
+            return
+        c1, c2 = self._codes_on(p.device)
+        for key, amk, x, code in (("state1", "absmax1", m, c1), ("state2", "absmax2", v, c2)):
+            codes, absmax = quantize_blockwise(x, code)
+            st[key].copy_(codes)
+            st[amk].copy_(absmax)
+
+    # -- the step ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0):
+        """One AdamW step over every parameter that has a gradient; ``grad_scale`` multiplies the gradients first (a clip
+        coefficient).  ``param_groups[i]["lr"]`` is read now, so a scheduler may drive it."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._ensure_state()
+        active = []
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse or p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.device != p.device:
+                    raise ValueError("AdamW8bit: gradients must be dense contiguous fp32 tensors on the parameter's device")
+                self.state[p]["step"] += 1
+                active.append((gi, p))
+        if not active:
+            return loss
+        if active[0][1].is_cuda or self.native_ops is not None:
+            self._step_hip(active, float(grad_scale))
+        else:
+            for gi, p in active:
+                g = self.param_groups[gi]
+                self._step_cpu(p, g["lr"], g["betas"], g["eps"], g["weight_decay"], float(grad_scale))
+        # The kernel writes the parameters behind torch's back: move one version counter so that engine.params_fingerprint changes
+        # and the native engines re-pack their weights (as FlatAdamW.step does).
+        active[0][1].add_(0.0)
+        return loss
+
+    def _step_cpu(self, p, lr, betas, eps, wd, scale):
+        """The definition, vectorised over one tensor: dequantise, AdamW in fp32 with every product and sum rounded separately
+        (the device kernel is compiled without fused multiply-adds so that both agree bit for bit on the moments), update the
+        parameter from the fresh moments, re-quantise block by block."""
+        f32 = np.float32
+        st, (is8, _, _) = self.state[p], self._layout[p]
+        n, step = p.numel(), st["step"]
+        b1, b2, lr, wd, eps, scale = f32(betas[0]), f32(betas[1]), f32(lr), f32(wd), f32(eps), f32(scale)
+        bc1 = f32(1) - np.power(b1, f32(step), dtype=f32)
+        bc2_sqrt = np.sqrt(f32(1) - np.power(b2, f32(step), dtype=f32), dtype=f32)
+        decay, step_size = f32(1) - lr * wd, lr / bc1
+        if is8:
+            m = dequantize_blockwise(st["state1"], st["absmax1"], self.code1, n)
+            v = dequantize_blockwise(st["state2"], st["absmax2"], self.code2, n)
+        else:
+            m, v = st["state1"], st["state2"]
+        gr = p.grad.reshape(-1) * float(scale)
+        pf = p.view(-1)
+        pf.mul_(float(decay))
+        m = m * float(b1) + gr * float(f32(1) - b1)
+        v = v * float(b2) + (gr * float(f32(1) - b2)) * gr
+        pf.sub_((m * float(step_size)) / (v.sqrt() / float(bc2_sqrt) + float(eps)))
+        if is8:
+            for key, amk, x, code in (("state1", "absmax1", m, self.code1), ("state2", "absmax2", v, self.code2)):
+                codes, absmax = quantize_blockwise(x, code)
+                st[key].copy_(codes)
+                st[amk].copy_(absmax)
+        else:
+            st["state1"].copy_(m)
+            st["state2"].copy_(v)
+
+    def _step_hip(self, active, grad_scale):
+        groups = self.param_groups
+        # one launch per distinct (betas, eps, step); the signature decides whether the cached table still describes this step
+        step0 = self.state[active[0][1]]["step"]
+        keys = [(groups[gi]["betas"][0], groups[gi]["betas"][1], groups[gi]["eps"], self.state[p]["step"] - step0) for gi, p in active]
+        sig = tuple((p.data_ptr(), p.grad.data_ptr(), k) for (gi, p), k in zip(active, keys))
+        if self._table is None or self._table["sig"] != sig:
+            order = sorted(range(len(active)), key=lambda i: keys[i])   # stable: parameters keep their order inside a launch
+            host = np.zeros(len(active), dtype=_TABLE_DTYPE)
+            launches, work, start = [], 0, 0
+            for j, i in enumerate(order):
+                gi, p = active[i]
+                if j > 0 and keys[i] != keys[order[j - 1]]:
+                    launches.append((start, j, work, keys[order[j - 1]]))
+                    start, work = j, 0
+                is8, b0, nb = self._layout[p]
+                host[j] = (p.data_ptr(), p.grad.data_ptr(), b0, p.numel(), work, 0.0, 0.0, 0 if is8 else 1, 0)
+                work += nb
+            launches.append((start, len(order), work, keys[order[-1]]))
+            dev = active[0][1].device
+            self._table = dict(sig=sig, host=host, launches=launches, group=np.array([active[i][0] for i in order]),
+                               dev=torch.empty(host.nbytes, dtype=torch.uint8, device=dev), uploaded=None)
+        t = self._table
+        t["host"]["lr"] = np.array([g["lr"] for g in groups], dtype=np.float32)[t["group"]]
+        t["host"]["weight_decay"] = np.array([g["weight_decay"] for g in groups], dtype=np.float32)[t["group"]]
+        image = t["host"].tobytes()
+        if t["uploaded"] != image:   # lr moves every scheduler step: 56 bytes per tensor
+            t["dev"].copy_(torch.frombuffer(bytearray(image), dtype=torch.uint8))
+            t["uploaded"] = image
+        a = self._arena
+        c1, c2 = self._codes_on(t["dev"].device)
+        ops = self.native_ops if self.native_ops is not None else _shared_ops()
+        opt = lambda x: x if x.numel() else None
+        import contextlib
+        with torch.cuda.device(t["dev"].device) if t["dev"].is_cuda else contextlib.nullcontext():
+            for start, end, work, (b1, b2, eps, dstep) in t["launches"]:
+                ops.adamw8_step(t["dev"][start * _TABLE_DTYPE.itemsize:], end - start, work, opt(a["s1"]), opt(a["s2"]), opt(a["a1"]),
+                                opt(a["a2"]), opt(a["f1"]), opt(a["f2"]), c1, c2, b1, b2, eps, step0 + dstep, grad_scale)
+
+    # -- checkpoints ---------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        self._ensure_state()
+        sd = super().state_dict()
+        for s in sd["state"].values():   # own copies: a pickled view would drag the whole arena along, once per tensor
+            for k, v in s.items():
+                if torch.is_tensor(v):
+                    s[k] = v.clone()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """This class's own state (codes, absmax, step per parameter) or a ``torch.optim.AdamW`` state (``exp_avg`` /
+        ``exp_avg_sq`` are quantised block-wise; small tensors keep them in fp32)."""
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups) or any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("AdamW8bit.load_state_dict: the parameter groups do not match")
+        id_map = {}
+        for s, g in zip(saved, self.param_groups):
+            id_map.update(zip(s["params"], g["params"]))
+            g.update({k: v for k, v in s.items() if k != "params"})
+        self._ensure_state()
+        for pid, s in state_dict["state"].items():
+            p = id_map[pid]
+            st, (is8, _, _) = self.state[p], self._layout[p]
+            if "exp_avg" in s:
+                self.set_moments(p, s["exp_avg"], s["exp_avg_sq"], step=int(s["step"]))
+                continue
+            if is8 != ("absmax1" in s) or s["state1"].numel() != st["state1"].numel():
+                raise ValueError("AdamW8bit.load_state_dict: saved state of another layout (min_8bit_size changed?)")
+            st["step"] = int(s["step"])
+            for k in ("state1", "state2") + (("absmax1", "absmax2") if is8 else ()):
+                st[k].copy_(s[k].to(st[k].dtype))
