@@ -15,7 +15,8 @@ The tape and the data gradients are the gradient engine's (engine_unet_bwd.py). 
 into one fp32 tensor per parameter (``plan["fgrads"]``), which the autograd bridge (unet3d._NativeStudentFull) hands to torch.
 The conditioning branch (time / fps / guidance MLPs, ``emb_layers``: B rows) stays with torch autograd behind ``emb_all``, as in LoRA
 training.  The weights change every optimizer step: the Packer re-fills its packs IN PLACE (``Packer.refresh``), so the recorded launch
-lists — raw device pointers — stay valid and nothing is re-recorded.
+lists — raw device pointers — stay valid and nothing is re-recorded.  Every plan (input signature) owns its Packer and is refreshed on
+its own, when its packs are behind the parameters.
 
 Correctness first: im2col is materialised (2 taps C bytes per output row) and every leaf's gradient is its own launches; the step is
 not a measured configuration of bench.py.  Verified on CPU against torch autograd through the module (tests/test_unet_full_grad_cpu.py),
@@ -36,9 +37,9 @@ class FullTrainMixin:
         """``params``: the parameters whose gradients the engine computes (every UNet parameter outside the conditioning branch)."""
         self.full_params = list(params)
         self.full_ids = {id(p) for p in self.full_params}
-        self.plans.clear()
+        self.plans.clear()             # (with every plan go its Packer, its weight fingerprint and its captured refresh)
         self.fingerprint = None
-        self._full_fp = None
+        self._last = None
 
     @property
     def training_full(self):
@@ -78,45 +79,81 @@ class FullTrainMixin:
         return out
 
     # ---- per-step pack refresh ------------------------------------------------------------------------------------------
-    def full_refresh_packs(self):
-        """Re-fill the weight packs in place when a parameter changed since the last forward (the launch lists keep their pointers)."""
+    # Every full-mode plan OWNS its Packer (``plan["owned"]``): its launch list holds the raw pointers of those packs.  So everything the
+    # refresh keeps lives IN THE PLAN — the fingerprint of the weights its packs were filled from (``full_fp``) and the captured refresh
+    # (``refresh``) — and goes with it when the plan is evicted, when ``bind_full`` drops all plans, or when it is recorded again.  A second
+    # input signature (the partial last batch of an epoch) then costs a second set of packs, and going back to the first plan after an
+    # optimizer step re-fills ITS packs first.  (One engine-wide fingerprint and ``self.pk`` = the Packer recorded last used to leave every
+    # other plan on bf16 packs of old weights next to live fp32 affines; one shared Packer instead would have to be brought up to date
+    # before every recording and re-captured whenever a new signature adds a pack.)
+    def full_activate(self, plan):
+        """Put the engine on ``plan``: the Packer its launches point into, and — for the closure backends of the tests, which re-run the
+        forward in Python — its pool, kept tensors and geometry."""
+        self.plan = plan
+        self.pool, self.pk, self.keep = plan["owned"]
+        self.B, self.F = plan["geom"]
+        self.device = plan["out"].device
+
+    def full_refresh_packs(self, plan):
+        """Re-fill the weight packs of ``plan`` in place when a parameter changed since they were filled (its launch list keeps its pointers)."""
         from .engine import params_fingerprint
         fp = params_fingerprint(self.model)
-        if getattr(self, "_full_fp", None) is None:
-            self._full_fp = fp
-        elif fp != self._full_fp:
-            self._refresh()
-            self._full_fp = fp
+        if fp != plan["full_fp"]:
+            self._refresh(plan)
+            plan["full_fp"] = fp
+
+    @property
+    def _refresh_state(self):
+        """The refresh bookkeeping of the plan that ran last (None: no refresh on the device yet); there is none outside the plans."""
+        last = getattr(self, "_last", None)
+        return None if last is None else last.get("refresh")
 
     # The refresh is ~ 2 000 small launches (torch copies / casts, library transposes and repacks) over FIXED tensors — the parameters'
     # storages in, the packs out — so after one eager pass it is captured as ONE hipGraph and replayed per optimizer step: the host's
-    # 15-17 ms of issuing it (tools/r6_gpu_calls/README.md, call 40) go.  The graph holds raw pointers: it is dropped and re-captured
-    # when a parameter was re-homed or a pack was added; T2V_REFRESH_GRAPH=0 keeps the eager loop.
+    # 15-17 ms of issuing it (tools/r6_gpu_calls/README.md, call 40) go.  The graph holds raw pointers: its signature names the Packer,
+    # every pack tensor and every parameter storage, and it is dropped and re-captured when a parameter was re-homed or a pack was added;
+    # T2V_REFRESH_GRAPH=0 keeps the eager loop.
     refresh_graph = os.environ.get("T2V_REFRESH_GRAPH", "1") == "1"
 
-    def _refresh(self):
+    @staticmethod
+    def _pack_ptrs(pk):
+        ptrs = []
+
+        def walk(v):
+            if isinstance(v, torch.Tensor):
+                ptrs.append(v.data_ptr())
+            elif isinstance(v, (tuple, list)):
+                for e in v:
+                    walk(e)
+        for v in pk.cache.values():
+            walk(v)
+        return tuple(ptrs)
+
+    def _refresh(self, plan):
+        pk = plan["owned"][1]
+        assert pk is self.pk, "the pack refresh runs on the Packer of the plan being replayed (full_activate)"
         dev = getattr(self, "device", None)
         if not (self.refresh_graph and getattr(self.ops, "is_native", False) and dev is not None and dev.type == "cuda"):
-            self.pk.refresh(self.ops)
+            pk.refresh(self.ops)
             return
         from .nn_util import walk_parameters
-        sig = (len(self.pk.makers), tuple(p.data_ptr() for p in walk_parameters(self.model)))
-        st = getattr(self, "_refresh_state", None)
+        sig = (id(pk), self._pack_ptrs(pk), tuple(p.data_ptr() for p in walk_parameters(self.model)))
+        st = plan.get("refresh")
         if st is not None and st["sig"] == sig and st["graph"] is not None:
             st["graph"].replay()
             return
         if st is None or st["sig"] != sig:
-            self.pk.refresh(self.ops)               # first pass for this set of tensors: eager (it also warms the allocator)
-            self._refresh_state = {"sig": sig, "graph": None, "failed": False}
+            pk.refresh(self.ops)                    # first pass for this set of tensors: eager (it also warms the allocator)
+            plan["refresh"] = {"sig": sig, "graph": None, "failed": False}
             return
         if st["failed"]:
-            self.pk.refresh(self.ops)
+            pk.refresh(self.ops)
             return
         try:                                         # second pass: capture, then run the captured pass
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize(dev)
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self.pk.refresh(self.ops)
+                pk.refresh(self.ops)
             g.replay()
             st["graph"] = g
         except Exception as e:  # noqa: BLE001 - a maker the capture cannot take (host read-back, pageable copy): stay eager, say so once
@@ -124,7 +161,7 @@ class FullTrainMixin:
             warnings.warn(f"pack refresh not capturable as a hipGraph ({type(e).__name__}: {e}); staying with the eager pass")
             st["failed"] = True
             torch.cuda.synchronize(dev)
-            self.pk.refresh(self.ops)
+            pk.refresh(self.ops)
 
     # ---- forward side: keep the leaf's input ----------------------------------------------------------------------------
     def full_save(self, mods, x, **info):

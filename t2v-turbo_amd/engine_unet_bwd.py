@@ -140,8 +140,8 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                 if self.training_lora:
                     self.refresh_lora_packs()
                 else:
-                    self.plan = plan
-                    self.full_refresh_packs()
+                    self.full_activate(plan)      # this plan's Packer (not the one recorded last), then ITS packs up to date
+                    self.full_refresh_packs(plan)
             if dropping:
                 st["seed"].fill_(self._seed)
             if "seed" in st:
@@ -169,6 +169,8 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         if plan.get("bwd_id") == plan["fwd_id"]:
             raise RuntimeError("UNet gradient: backward was already run for this forward (its saved activations are gone)")
         plan["bwd_id"] = plan["fwd_id"]
+        if self.training_full:
+            self.full_activate(plan)              # (another signature's forward may have run since this plan's)
         st = plan["static"]
         st["dout"].zero_() if dout is None else st["dout"].copy_(dout)
         dprobs = dprobs or {}
@@ -304,8 +306,9 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             plan["fgrads"] = {}
             st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
             self.seed_t = st["seed"]
-            self._full_fp = None
-            self.full_refresh_packs()
+            from .engine import params_fingerprint
+            plan["full_fp"] = params_fingerprint(m)   # the weights this plan's packs are made from, while it is recorded
+        plan["geom"] = (B, F)
         self.plan = plan
         self.tape, self.refs = [], {}
         self._fsaved = {}

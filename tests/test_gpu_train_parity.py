@@ -620,6 +620,49 @@ def _body_overlapped_gradient_exchange_over_rccl_one_rank():
 
 
 # ------------------------------------------------------------------------------------------------------------- (v) full fine-tuning
+def _seeded_update(ref, m, gen, factor=0.03):
+    """An optimizer-style step of every weight, the same on the fp32 CPU reference module and on the module under test."""
+    with torch.no_grad():
+        for p, q in zip(ref.parameters(), m.parameters()):
+            d = torch.randn(p.shape, generator=gen) * factor * float(p.abs().mean() + 1e-3)
+            p.add_(d)
+            q.add_(d.to(q.device))
+
+
+def _module_route(dev):
+    """"auto" on the device (the route must find the native engine by itself); the CPU dry runs of these bodies name it."""
+    return "auto" if torch.device(dev).type == "cuda" else "train"
+
+
+def _full_step_vs_cpu_autograd(ref, m, cpu_args, kw, prev, tag, out_tol=OUT_TOL, dx_tol=DX_TOL, cos_min=0.97, cos_median=0.995):
+    """One step of ``m`` through the module route against fp32 CPU autograd through ``ref`` (the same weights).  ``prev``: the reference's
+    (output, d/d latents) for these inputs at the PREVIOUS weights (None: no update since).  Pins the margin that makes stale packs visible:
+    the reference itself must have moved by more than 3x the tolerances, and the result must be nearer the current reference than the
+    previous one — a step on packs of the old weights fails, and so does an update scale too small for these checks to see one."""
+    from tests.test_unet_full_grad_cpu import _fixture_step
+    dev = next(m.parameters()).device
+    y_r, dx_r, g_r = _fixture_step(ref, *cpu_args, "off", **kw)
+    kw_dev = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
+    y, dx, grads = _fixture_step(m, *(t.to(dev) for t in cpu_args), _module_route(dev), **kw_dev)
+    y, dx = y.cpu(), dx.cpu()
+    e_out, e_dx = rel_l2(y, y_r), rel_l2(dx, dx_r)
+    cos = torch.tensor([float(torch.nn.functional.cosine_similarity(a.cpu().double().reshape(1, -1), b.double().reshape(1, -1)))
+                        for a, b in zip(grads, g_r) if float(b.abs().max()) > 0])
+    line = f"[full fine-tuning, {tag}] out {e_out:.3e} dx {e_dx:.3e}; gradient cosine min {float(cos.min()):.4f} median {float(cos.median()):.4f}"
+    if prev is not None:
+        y_p, dx_p = prev
+        m_out, m_dx = rel_l2(y_r, y_p), rel_l2(dx_r, dx_p)
+        r_out_, r_dx = e_out / rel_l2(y, y_p), e_dx / rel_l2(dx, dx_p)
+        line += f"; the reference moved out {m_out:.3e} dx {m_dx:.3e}; distance to current / to previous reference: out {r_out_:.3f} dx {r_dx:.3f}"
+    print(line, flush=True)
+    if prev is not None:
+        assert m_out > 3 * OUT_TOL and m_dx > 3 * DX_TOL, f"{tag}: the update must move the reference far beyond the tolerances for this check to mean anything"
+        assert r_out_ < 0.5 and r_dx < 0.5, f"{tag}: nearer the reference at the PREVIOUS weights than expected of up-to-date packs"
+    assert e_out < out_tol and e_dx < dx_tol, tag
+    assert float(cos.min()) > cos_min and float(cos.median()) > cos_median, tag
+    return y_r, dx_r
+
+
 def test_full_fine_tuning_on_device_vs_the_reference_gradient_fixture():
     """Row a20 (train_latent_t2v_turbo_v2.py:669,798-816,1262: every UNet parameter trainable, no LoRA) on MI355X: the module route lands on
     the native gradient engine with base-weight gradients (engine_full.py: t2v_wgrad_tn / t2v_im2col_bf16 / t2v_norm_affine_grad), WITHOUT
@@ -653,26 +696,108 @@ def test_full_fine_tuning_on_device_vs_the_reference_gradient_fixture():
     # as one hipGraph, the third replays it (engine_full._refresh)
     plan = next(iter(m._engine_box.full.plans.values()))
     gen = torch.Generator().manual_seed(5)
-    y_prev = gg["out"]
+    prev = (gg["out"], gg["dx"])
     for upd in range(3):
-        with torch.no_grad():
-            for p, q in zip(ref.parameters(), m.parameters()):
-                d = torch.randn(p.shape, generator=gen) * 0.03 * float(p.abs().mean() + 1e-3)
-                p.add_(d)
-                q.add_(d.cuda())
-        y_r, dx_r, g_r = _fixture_step(ref, g["x"], g["ts"], g["ctx"], g["tc"], r_out, "off")
-        y, dx, grads = _fixture_step(m, *args, "auto")
+        _seeded_update(ref, m, gen)
+        prev = _full_step_vs_cpu_autograd(ref, m, (g["x"], g["ts"], g["ctx"], g["tc"], r_out), {}, prev, f"after update {upd + 1}")
         assert next(iter(m._engine_box.full.plans.values())) is plan
-        assert rel_l2(y_r, y_prev) > 1e-3, "the update must change the output for this check to mean anything"
-        y_prev = y_r
-        assert rel_l2(y.cpu(), y_r) < OUT_TOL and rel_l2(dx.cpu(), dx_r) < DX_TOL, upd
-        cos = torch.tensor([float(torch.nn.functional.cosine_similarity(a.cpu().double().reshape(1, -1), b.double().reshape(1, -1)))
-                            for a, b in zip(grads, g_r) if float(b.abs().max()) > 0])
-        print(f"[full fine-tuning, after update {upd + 1}] gradient cosine min {float(cos.min()):.4f} median {float(cos.median()):.4f}", flush=True)
-        assert float(cos.min()) > 0.97 and float(cos.median()) > 0.995, upd
     eng = m._engine_box.full
     if eng.refresh_graph:
         assert eng._refresh_state["graph"] is not None and not eng._refresh_state["failed"], "the pack refresh was not captured"
+
+
+def test_full_fine_tuning_two_signatures_on_device():
+    """Two input signatures with optimizer steps between their visits (the data loader of train_latent_t2v_turbo_v2.py keeps the partial
+    last batch): A = the unet_tiny inputs, B = the same with the latent cropped to 2 frames.  A, update, A, update, A (one eager pack
+    refresh, then the captured one); then B is recorded, and update / B / update / A / update / B — every step against fp32 CPU autograd
+    at the current weights.  Each plan owns its Packer and its captured refresh: B's first refresh must not replay A's graph into A's
+    packs, and A must be refreshed when the engine comes back to it."""
+    run_full_fine_tuning_two_signatures(torch.device("cuda", 0), None)
+
+
+def run_full_fine_tuning_two_signatures(dev, emu_factory, out_tol=OUT_TOL, dx_tol=DX_TOL, cos_min=0.97, cos_median=0.995):
+    import copy
+    import warnings
+    from oracle.synth import synth_state_dict
+    from t2v_turbo_amd.unet3d import UNetModel
+    g = load("unet_tiny")
+    ref = UNetModel(**tiny_unet_params())
+    ref.load_state_dict(synth_state_dict(manifest("unet_tiny")), strict=True)
+    ref.requires_grad_(True)
+    ref.eval()
+    m = copy.deepcopy(ref).to(dev)
+    if emu_factory is not None:
+        m._native_ops_factory = emu_factory
+    xa = g["x"]
+    xb = xa[:, :, :2].contiguous()
+    sigs = {"A": (xa, g["ts"], g["ctx"], g["tc"], torch.randn(xa.shape, generator=torch.Generator().manual_seed(9))),
+            "B": (xb, g["ts"], g["ctx"], g["tc"], torch.randn(xb.shape, generator=torch.Generator().manual_seed(10)))}
+    prev = {"A": None, "B": None}
+    gen = torch.Generator().manual_seed(5)
+    tol = dict(out_tol=out_tol, dx_tol=dx_tol, cos_min=cos_min, cos_median=cos_median)
+    plans = {}
+    # (B is recorded at the weights A last ran at; every other step follows an update.  ``prev[name]``: the reference at that signature's
+    # LAST visit — the weights its packs would still hold if they were not re-filled)
+    for i, (name, update) in enumerate([("A", False), ("A", True), ("A", True), ("B", False), ("B", True), ("A", True), ("B", True)]):
+        if update:
+            _seeded_update(ref, m, gen)
+        assert update == (prev[name] is not None)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")     # the ATen-route warning must not fire
+            prev[name] = _full_step_vs_cpu_autograd(ref, m, sigs[name], {}, prev[name], f"two signatures, step {i + 1}: {name}", **tol)
+        eng = m._engine_box.full
+        plans.setdefault(name, eng._last)
+        assert eng._last is plans[name] and len(eng.plans) == len(plans), "a plan was recorded again"
+        assert eng.pk is eng._last["owned"][1]
+    assert plans["A"]["owned"][1] is not plans["B"]["owned"][1]
+    assert "_full_fp" not in vars(eng) and "_refresh_state" not in vars(eng)      # no refresh state outside the plans
+    if eng.refresh_graph and torch.device(dev).type == "cuda":
+        for name, plan in plans.items():
+            st = plan.get("refresh")
+            assert st is not None and st["graph"] is not None and not st["failed"], f"the pack refresh of plan {name} was not captured"
+            assert st["sig"][0] == id(plan["owned"][1])            # each captured refresh writes into its own plan's Packer
+        assert eng._refresh_state is plans["B"]["refresh"] and eng._refresh_state["sig"][0] == id(eng.pk)
+
+
+def test_full_fine_tuning_batch2_motion_cond_on_device_vs_the_reference_fixture():
+    """B = 2 with two timesteps, fps = 8 and ``motion_cond`` (train_latent_t2v_turbo_v2.py --train_batch_size > 1 --use_motion_cond) against
+    tests/golden/unet_tiny_mg_b2_full_grad.npz, the reference's own gradients of all 1487 parameters: the per-clip column sums behind
+    d(loss)/d(emb_all), the per-clip text K / V weight gradients, motion_cond_proj / combine_proj behind ``emb_all``.  Recording pass and
+    one replay; then one weight update checked against fp32 CPU autograd."""
+    run_full_fine_tuning_batch2_motion_cond(torch.device("cuda", 0), None, (OUT_TOL, DX_TOL, 0.10, (0.30, 0.06), 0.12))
+
+
+def run_full_fine_tuning_batch2_motion_cond(dev, emu_factory, fixture_tol, **tol):
+    import copy
+    import warnings
+    from oracle.synth import synth_state_dict
+    from t2v_turbo_amd.unet3d import UNetModel
+    from tests.golden.make_golden_full_grad import SEED_R
+    from tests.test_unet_full_grad_cpu import _fixture_step, check_against_reference_fixture
+    g, gg = load("unet_tiny_mg_b2"), load("unet_tiny_mg_b2_full_grad")
+    ref = UNetModel(**tiny_unet_params(motion_cond_proj_dim=256))
+    ref.load_state_dict(synth_state_dict(manifest("unet_tiny_mg_b2")), strict=True)
+    ref.requires_grad_(True)
+    ref.eval()
+    m = copy.deepcopy(ref).to(dev)
+    if emu_factory is not None:
+        m._native_ops_factory = emu_factory
+    names = [n for n, _ in m.named_parameters()]
+    r_out = torch.randn(g["x"].shape, generator=torch.Generator().manual_seed(SEED_R))
+    cpu_args = (g["x"], g["ts"], g["ctx"], g["tc"], r_out)
+    for rep in range(2):   # recording pass, then a replay
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")     # the ATen-route warning must not fire: the route is train_full
+            assert m._auto_route(g["x"].to(dev).clone().requires_grad_(True), g["ctx"].to(dev), g["tc"].to(dev), None)[0] == "train_full"
+            y, dx, grads = _fixture_step(m, *(t.to(dev) for t in cpu_args), _module_route(dev), 8, g["mc"].to(dev))
+        assert m._engine_box.full is not None and len(m._engine_box.full.plans) == 1
+        check_against_reference_fixture(y.cpu(), dx.cpu(), [t.cpu() for t in grads], names, gg, *fixture_tol)
+    plan = next(iter(m._engine_box.full.plans.values()))
+    _seeded_update(ref, m, torch.Generator().manual_seed(5))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        _full_step_vs_cpu_autograd(ref, m, cpu_args, dict(fps=8, mc=g["mc"]), (gg["out"], gg["dx"]), "B = 2 motion_cond, after the update", **tol)
+    assert next(iter(m._engine_box.full.plans.values())) is plan and len(m._engine_box.full.plans) == 1
 
 
 def test_full_fine_tuning_mid_width_on_device_vs_the_reference_gradient_fixture():

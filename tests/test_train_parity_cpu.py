@@ -3,12 +3,26 @@
 replay with the masks REGENERATED from the recorded site geometry (what the GPU test has to do: the device keeps no masks)."""
 import torch
 
-from tests.emu_ops import EmuOps
-from tests.test_gpu_train_parity import run_student_train_mode_vs_reference_oracle, run_train_mode_with_replayed_masks, run_trainer_route
+from tests.emu_ops import EmuOps, ReplayOps
+from tests.test_gpu_train_parity import (run_full_fine_tuning_batch2_motion_cond, run_full_fine_tuning_two_signatures,
+                                         run_student_train_mode_vs_reference_oracle, run_train_mode_with_replayed_masks, run_trainer_route)
 
 
 def test_trainer_route_two_steps_cpu():
     run_trainer_route(torch.device("cpu"), lambda: EmuOps(strict=True), 1e-4, 0.9999)
+
+
+def test_full_fine_tuning_two_signatures_cpu():
+    """Dry run of test_full_fine_tuning_two_signatures_on_device under the record / replay protocol at fp32: the same sequence of steps and
+    updates, the same guards on how far the reference moved, fp32 tolerances."""
+    run_full_fine_tuning_two_signatures(torch.device("cpu"), ReplayOps, out_tol=2e-5, dx_tol=3e-4, cos_min=0.99999, cos_median=0.999999)
+
+
+def test_full_fine_tuning_batch2_motion_cond_cpu():
+    """Dry run of test_full_fine_tuning_batch2_motion_cond_on_device_vs_the_reference_fixture: the native route against the REFERENCE's own
+    B = 2 / motion_cond gradients at fp32 tolerances."""
+    run_full_fine_tuning_batch2_motion_cond(torch.device("cpu"), ReplayOps, (2e-5, 3e-4, 3e-4, (3e-3, 3e-4), 3e-4),
+                                            out_tol=2e-5, dx_tol=3e-4, cos_min=0.99999, cos_median=0.999999)
 
 
 def test_train_mode_regenerated_masks_cpu():
