@@ -18,6 +18,11 @@ training.  The weights change every optimizer step: the Packer re-fills its pack
 lists — raw device pointers — stay valid and nothing is re-recorded.  Every plan (input signature) owns its Packer and is refreshed on
 its own, when its packs are behind the parameters.
 
+Activation checkpointing (``checkpoint_blocks``, the yaml's ``use_checkpoint: true``) works with this mixin: what it keeps per leaf between
+forward and backward is ``_fsaved`` alone, and ``engine_unet_bwd.checkpointed`` rewinds it with a block's discarded forward
+(``full_mark`` / ``full_rewind``); the recomputation inside the block's backward saves the same leaves again and the leaf backwards take
+them.  Same gradients bit for bit (tests/test_unet_full_ckpt_cpu.py, tests/test_gpu_full_ckpt.py).
+
 Correctness first: im2col is materialised (2 taps C bytes per output row) and every leaf's gradient is its own launches; the step is
 not a measured configuration of bench.py.  Verified on CPU against torch autograd through the module (tests/test_unet_full_grad_cpu.py),
 on the host simulator per kernel, and on MI355X against the imported reference's own parameter gradients (tests/golden/unet_tiny_full_grad.npz)."""
@@ -168,15 +173,37 @@ class FullTrainMixin:
         if any(is_lora_leaf(mm) for mm in mods):
             raise NotImplementedError("native full fine-tuning of a LoRA-injected network (train the LoRA tensors, or merge them first)")
         key = tuple(id(mm) for mm in mods)
-        old = self._fsaved.pop(key, None)
-        if old is not None:   # (a checkpointed block's recomputation saves again)
-            self.drop(*old[0].parts)
+        assert key not in self._fsaved, "a leaf input is saved once per forward (a checkpointed block's discarded forward is rewound: full_rewind)"
         self.hold(*x.parts)
         self._fsaved[key] = (x, info)
 
     def full_take(self, mods):
         x, info = self._fsaved.pop(tuple(id(mm) for mm in mods))
         return x, info
+
+    # ---- activation checkpointing (engine_unet_bwd.checkpointed) --------------------------------------------------------
+    # Everything this mixin keeps between a leaf's forward and its backward is in ``_fsaved``: the leaf's input Act (both parts of a
+    # virtual concat; one entry for a q | k | v group) and the GEGLU row permutation.  The rest is either in the block's closures — the
+    # GroupNorm statistics ``full_norm_grads`` reads and the per-clip text K / V of ``own_kv`` are pool buffers the discarded forward
+    # gives back and the recomputation allocates again — or written by the backward alone: the ``d_emb`` column sums (once, from the
+    # recomputed block's own backward) and the gradient arena, which is made at the first ``fgrad`` of the backward recording whether
+    # that is the exit conv's or a recomputed block's.
+    def full_mark(self):
+        """How many leaf inputs are saved (taken before a checkpointed block runs).  Saving appends to ``_fsaved`` and a block takes only what
+        it saved itself, so the entries older than a mark keep their places: what came after it is the tail of the insertion order."""
+        return len(self._fsaved)
+
+    def full_since(self, mark):
+        """Leaf keys saved after ``mark`` and not taken yet, in saving order."""
+        return list(self._fsaved)[mark:]
+
+    def full_rewind(self, mark):
+        """Forget what a block's discarded forward saved since ``mark`` -> those keys.  No ``drop``: the caller released the block's buffers
+        and rewound ``refs``; what the block held of tensors older than itself stays held until its backward (``extra``)."""
+        gone = self.full_since(mark)
+        for k in gone:
+            del self._fsaved[k]
+        return gone
 
     def fgrad(self, p):
         """The fp32 gradient tensor of parameter ``p``: a view into the plan's gradient arena (one allocation for all parameters, made at the

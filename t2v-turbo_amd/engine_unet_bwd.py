@@ -47,9 +47,14 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
     # BasicTransformerBlock._forward, attention.py:300-311; yaml ``use_checkpoint: true``): with ``checkpoint_blocks`` every
     # residual block and every spatial / temporal transformer keeps only its INPUT in the forward and re-runs its forward inside
     # the backward (the counter-based dropout masks regenerate from (seed, site), so the recomputation is the same function).
-    # Same gradients bit for bit, fewer live activations, one more block forward per block.  Default off: the tape of a
-    # full-size step is 43 GB of 288.  T2V_NATIVE_CHECKPOINT=1 turns it on, =model follows the module's own ``use_checkpoint``
-    # (what the reference's yaml sets), or set the attribute before the first forward.
+    # Same gradients bit for bit, fewer live activations, one more block forward per block.  LoRA training and full fine-tuning
+    # alike: under ``bind_full`` the leaf inputs kept for the weight gradients are rewound with the block's discarded forward and
+    # saved again by its recomputation (engine_full.full_rewind).  Default off: at full size and B = 1 the full fine-tuning
+    # step's activation pool is 20.2 GB on the tape (6.9 GB checkpointed) inside a 44.6 GB peak of the process, of 288
+    # (profiles/r08_full_finetune_checkpoint_memory.jsonl), and checkpointing costs a fifth of the step.
+    # T2V_NATIVE_CHECKPOINT=1 turns it on, =model follows the module's own ``use_checkpoint`` (what the reference's yaml
+    # sets); ``UNetModel.native_checkpoint`` = True / False overrides the variable per module, and the attribute below can be set
+    # on an engine at any time (a change of mode drops the recorded plans).
     _ckpt_env = os.environ.get("T2V_NATIVE_CHECKPOINT", "0")
     _ckpt_set = None
 
@@ -63,9 +68,11 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
 
     @checkpoint_blocks.setter
     def checkpoint_blocks(self, on):
-        if bool(on) != self.checkpoint_blocks:
+        """True / False, or None: back to what T2V_NATIVE_CHECKPOINT says."""
+        before = self.checkpoint_blocks
+        self._ckpt_set = None if on is None else bool(on)
+        if self.checkpoint_blocks != before:
             self.plans.clear()                      # recorded launch lists are specific to the mode
-        self._ckpt_set = bool(on)
 
     def __init__(self, model, ops):
         super().__init__(model, ops)
@@ -296,9 +303,6 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
             self.seed_t = st["seed"]
         if self.training_full:
-            if self.checkpoint_blocks:
-                raise NotImplementedError("native full fine-tuning with checkpoint_blocks (the leaf inputs a recomputed block saves again "
-                                          "are not covered by tests): leave T2V_NATIVE_CHECKPOINT off — the tape of a full-size step fits 288 GB")
             # plain leaves on packs of the current weights (re-filled in place per step: Packer.refresh); one fp32 gradient per parameter
             self.pk = Packer(self.adt, x.device)
             st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
@@ -770,6 +774,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             else:
                 d = fn(d)
         self.entry_bwd(d, dx_out)
+        assert not (self.training_full and self._fsaved), "full fine-tuning: a saved leaf input was not taken by any backward"
         if self.training_lora:
             self._seg_emit_down_to(0)   # whatever is left of the arena (and every piece, if some group never finished)
 
@@ -788,6 +793,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         live0, refs0 = set(pool.live), dict(self.refs)
         n_tape, n_sites = len(self.tape), len(self.drop_sites)
         saved0 = {k: g.saved for k, g in getattr(self, "_groups", {}).items()}
+        fmark = self.full_mark() if self.training_full else None
         y = block_t(layer, h)
         assert len(self.tape) == n_tape + 1 and self.tape[-1][0] == "block"
         if len(self.plan["probs"]) != n_probs:
@@ -812,13 +818,19 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         for k, g in getattr(self, "_groups", {}).items():
             if g.saved is not saved0.get(k):
                 g.saved = None
+        if fmark is not None:
+            # full fine-tuning: the leaf inputs the discarded forward recorded (their buffers went back to the pool above, and their
+            # holds were rewound with ``refs``); the recomputation saves them again, and the block's backward takes them
+            leaves_fwd = self.full_rewind(fmark)
         sites_fwd = self.drop_sites[n_sites:]
 
         def bwd(dy):
             outer_tape, outer_sites = self.tape, self.drop_sites
             self.tape, self.drop_sites = [], outer_sites[:n_sites]   # the block's dropout sites get the numbers they had
+            fmark2 = self.full_mark() if self.training_full else None
             y2 = block_t(layer, h)
             assert [(k, m) for _, k, m in self.drop_sites[n_sites:]] == [(k, m) for _, k, m in sites_fwd]
+            assert fmark2 is None or self.full_since(fmark2) == leaves_fwd, "the recomputation saved other leaf inputs than the forward"
             sub, self.tape, self.drop_sites = self.tape, outer_tape, outer_sites
             for p in y2.parts:                      # the recomputed output itself is not needed
                 if self.refs.get(p.data_ptr(), 0) == 0 and p.data_ptr() in pool.live:
@@ -827,6 +839,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             for kind, fn in reversed(sub):
                 assert kind == "block"
                 d = fn(d)
+            assert fmark2 is None or not self.full_since(fmark2), "a recomputed leaf input was not taken by the block's backward"
             for q, n in extra.items():              # the first forward's holds (the recomputation took and dropped its own)
                 left = self.refs.get(q, 0) - n
                 if left > 0:

@@ -652,6 +652,23 @@ class UNetModel(nn.Module):
             self._engine_box.engine = UNetEngine(self, HipOps())
         return self._engine_box.engine
 
+    # ---- activation checkpointing on the native training engines (UNetGradEngine.checkpoint_blocks) --------------------------------
+    @property
+    def native_checkpoint(self):
+        """None (default): the gradient engines follow T2V_NATIVE_CHECKPOINT [0 | 1 | model]; True / False: checkpointing on / off for the
+        engines of this module — every residual block and spatial / temporal transformer keeps only its input and is recomputed inside the
+        backward (the reference's ``use_checkpoint``).  Applied when an engine is built; setting it later goes through the engines'
+        ``checkpoint_blocks`` setter, which drops their recorded plans when the mode changes."""
+        return self.__dict__.get("_native_checkpoint")
+
+    @native_checkpoint.setter
+    def native_checkpoint(self, on):
+        self.__dict__["_native_checkpoint"] = None if on is None else bool(on)
+        for slot in ("full", "grad", "enc"):
+            eng = getattr(self._engine_box, slot, None)
+            if eng is not None:
+                eng.checkpoint_blocks = self.native_checkpoint
+
     # ---- native FULL fine-tuning (every parameter trainable, no LoRA: train_latent_t2v_turbo_v2.py) ---------------------------------
     native_full = os.environ.get("T2V_NATIVE_FULL", "1") == "1"
 
@@ -662,6 +679,7 @@ class UNetModel(nn.Module):
             if make_ops is None:
                 from .native import HipOps as make_ops
             eng = UNetGradEngine(self, make_ops())
+            eng.checkpoint_blocks = self.native_checkpoint
             eng.bind_full(eng.engine_parameters(self))
             self._engine_box.full = eng
         return self._engine_box.full
@@ -691,6 +709,7 @@ class UNetModel(nn.Module):
             if make_ops is None:
                 from .native import HipOps as make_ops
             eng = UNetGradEngine(self, make_ops())
+            eng.checkpoint_blocks = self.native_checkpoint
             eng.bind_lora(lora.lora_parameters(self))
             setattr(self._engine_box, slot, eng)
         return getattr(self._engine_box, slot)
