@@ -266,7 +266,10 @@ int t2v_conv3x3_small_cout(const void* x, int ldx, int n_img, int h, int w, int 
  * rows_per_unit consecutive rows.  Replaces GroupNormSpecific / nn.GroupNorm (+ nn.SiLU)
  * (lvdm/basics.py:78-89; openaimodel3d.py:155-157,179-181,275-292,666-668;
  * attention.py:340-342,422-424; ae_modules.py:11-19).
- * ws: fp32 workspace of t2v_gn_ws_floats(...) floats.  stats out: [n_units][groups][2] = (mean, rstd). */
+ * ws: fp32 workspace of t2v_gn_ws_floats(...) floats.  stats out: [n_units][groups][2] = (mean, rstd).
+ * Row strides: multiples of 8, ld0 >= c0, ld1 >= c1, ldo >= c0 + c1 (checked; the same holds for every normalisation entry point below
+ * and for their backward forms).  Only the c0 / c1 columns of a row are read, only the first c0 + c1 columns of an output row and the
+ * first *_ws_floats floats of a workspace are written. */
 long long t2v_gn_ws_floats(int n_units, int rows_per_unit, int groups);
 int t2v_gn_stats(const void* x0, int c0, int ld0, const void* x1, int c1, int ld1, int n_units,
                  int rows_per_unit, int groups, float eps, float* ws, float* stats, void* stream);
@@ -302,12 +305,14 @@ int t2v_group_norm_cs(const float* cs0, const float* cs1, const void* x0, int c0
 int t2v_gn_stats_cs(const float* cs0, int c0, const float* cs1, int c1, int n_units, int rows_per_unit, int groups, float eps,
                     float* ws, float* stats, void* stream);
 
-/* LayerNorm over the channel dim, eps, affine; bf16 in/out (attention.py:279-281). */
+/* LayerNorm over the channel dim, eps, affine; bf16 in/out (attention.py:279-281).  C % 8 == 0, ldx, ldo multiples of 8 and >= C. */
 int t2v_layernorm(const void* x, int ldx, int M, int C, const float* gamma, const float* beta,
                   float eps, void* out, int ldo, void* stream);
 
 /* row softmax in place on bf16 [rows][ld]: cols [0,n) normalised, cols [n, n_pad) set to 0
- * (score matrix of the GEMM-formulated attention: attention.py:143, ae_modules.py:61). */
+ * (score matrix of the GEMM-formulated attention: attention.py:143, ae_modules.py:61).  n_pad % 8 == 0, n_pad <= ld, ld % 8 == 0.
+ * Columns [n, n_pad) are loaded but their values are never used (any bit pattern, NaN included); columns [n_pad, ld) are neither
+ * read nor written. */
 int t2v_softmax_rows(void* s, long long rows, int n, int n_pad, int ld, void* stream);
 
 /* ---------------------------------------------------------------- attention
@@ -315,8 +320,10 @@ int t2v_softmax_rows(void* s, long long rows, int n, int n_pad, int ld, void* st
  * q: bf16 rows (img*seq_q + i), head h at columns [h*64, h*64+64); k likewise over seq_kv rows;
  * vt: V transposed per image: bf16 [img_kv][heads*64][ld_vt] (keys contiguous); vt_img_stride = elements
  * between consecutive kv images (0 = heads*64*ld_vt; larger when several layers' V^T share one buffer).
- * ld_vt >= seq_kv rounded up to 64; the padding columns are read (their probability is exactly 0) and
- * must hold finite values.
+ * ld_vt >= seq_kv rounded up to 64; the padding columns up to that multiple of 64 are read (their probability is exactly 0) and
+ * must hold finite values; columns beyond it, and the space between two images when vt_img_stride > heads*64*ld_vt, are not read.
+ * K rows past seq_kv are not read (the tail of the last key tile comes from the library's zero page).  ldq, ldk % 8 == 0, ldo % 4 == 0,
+ * all >= heads*64.  The probabilities enter the P V product rounded to bf16 (fp32 accumulation).
  * kv image of q image b is b / kv_div (text cross-attention shares K/V across the frames of a clip).
  * Replaces CrossAttention.forward / efficient_forward (attention.py:102-164,166-240 = xformers
  * memory_efficient_attention). */
@@ -328,7 +335,7 @@ int t2v_attn_spatial(const void* q, int ldq, const void* k, int ldk, const void*
  * softmax(Q K^T * scale) V over the F frames, reading rows ((b*F+f)*HW + p) directly from the
  * token-major q/k/v (no '(b h w) t c' rearrange copies, attention.py:475-511,102-164).
  * probs (optional, fp32 [(b*HW+p)*heads+h][F][F]) = CrossAttention.attention_probs
- * (attention.py:124-126). */
+ * (attention.py:124-126).  Row strides: multiples of 8, >= heads*64; only the heads*64 columns of a row are read / written. */
 int t2v_attn_temporal(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                       void* out, int ldo, int n_clips, int frames, int hw, int heads, float scale,
                       float* probs, void* stream);
@@ -383,7 +390,8 @@ int t2v_gn_coop_error(void);
  * Conv / linear data gradients are t2v_gemm launches on re-packed weights; these are the non-GEMM parts.
  * t2v_gn_bwd: dx = d/dx [act(GroupNorm(x))] . dy (+ resid), act = SiLU or identity; stats = (mean, rstd) per
  *   (unit, group) from t2v_gn_stats of the forward; ws: t2v_gn_bwd_ws_floats() floats.  x, dy, resid, dx bf16.
- * t2v_softmax_bwd_rows: dp <- p * (dp - sum_j p_j dp_j) per row (columns >= n set to 0).
+ * t2v_softmax_bwd_rows: dp <- p * (dp - sum_j p_j dp_j) per row (columns [n, n_pad) set to 0; their p / dp inputs are loaded but never
+ *   used: any bit pattern; columns [n_pad, ld) neither read nor written).
  * t2v_transpose_bf16: out[b][c][r] = in[b][r][c].   t2v_sumpool2x2: adjoint of nearest-x2 upsampling (token-major). */
 long long t2v_gn_bwd_ws_floats(int n_units, int rows_per_unit, int groups);
 int t2v_gn_bwd(const void* x, int ldx, int C, int n_units, int rows_per_unit, int groups, const float* stats,
@@ -408,7 +416,9 @@ int t2v_sumpool2x2(const void* in, int n_img, int h, int w, int C, void* out, vo
  *   flipped 3x3 s1 p1 conv over this (openaimodel3d.py:63-72).
  * t2v_add_bf16: out = a + b over [M][C] with row strides (gradient fan-in at the skip connections).
  * t2v_attn_temporal_bwd: (dq, dk, dv) of t2v_attn_temporal from d(out) and, optionally, d(probs)
- *   (fp32 [(b*HW+p)*heads+h][F][F], the layout of the forward's probs output); frames <= 16. */
+ *   (fp32 [(b*HW+p)*heads+h][F][F], the layout of the forward's probs output); frames <= 16; input row strides % 8, gradient row
+ *   strides % 4, all >= heads*64; P and dS enter the MFMAs rounded to bf16.
+ * Every row stride of this section must be >= the row's width (checked). */
 int t2v_gn_bwd2(const void* x0, int c0, int ld0, const void* x1, int c1, int ld1, int n_units, int rows_per_unit, int groups,
                 const float* stats, const float* gamma, const float* beta, int silu, const void* dy, int ldy, const void* resid,
                 int ldr, float* ws, void* dx, int ldo, void* stream);
@@ -488,7 +498,12 @@ int t2v_gather_f32(const float* src, const int* idx, float alpha, void* out, int
  * q, k, dout, o, dq, dk, dv: bf16 [n_img*seq][ld], head h at column 64 h.  v: bf16, row r of (img, head) at
  * v + img*v_img_stride + head*v_head_stride + r*ldv (token-major buffer or the per-head [keys][64] transpose of V^T).
  * kt, qt, dot: K^T, Q^T, dO^T per image, [n_img][heads*64][ld] with the sequence zero-padded to a multiple of 64
- * (t2v_transpose_pad_bf16).  l2, dsum: fp32 workspaces [n_img*heads][ld_stat], ld_stat >= seq_q.
+ * (t2v_transpose_pad_bf16): the padding columns up to that multiple of 64 ARE read and must be zero, columns beyond it are not read.
+ * V rows r >= seq_kv (the padding rows of the per-head layout) and K / Q / dO rows past the sequence are not read (zero page).
+ * l2, dsum: fp32 workspaces [n_img*heads][ld_stat], ld_stat >= seq_q; only columns [0, seq_q) are written.
+ * D is computed from the bf16 O the caller passes; P and dS enter the MFMAs rounded to bf16.  seq_q != seq_kv is supported (K / V / kt /
+ * dk / dv over seq_kv rows per image, the rest over seq_q).  Strides: ldq, ldk, ldv, ld_kt, ld_qt, ldo, ldoo % 8, lddq, lddk, lddv % 4,
+ * token-major strides >= heads*64, ldv >= 64, ld_kt >= roundup(seq_kv, 64), ld_qt >= roundup(seq_q, 64) (checked).
  * Replaces the autograd backward of CrossAttention.forward for attn1 of the spatial transformers (attention.py:102-164). */
 int t2v_attn_spatial_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, long long v_img_stride,
                          long long v_head_stride, const void* kt, int ld_kt, const void* qt, const void* dot, int ld_qt,

@@ -650,6 +650,7 @@ extern "C" int t2v_attn_spatial(const void* q, int ldq, const void* k, int ldk, 
     T2V_REQUIRE(q && k && vt && out, T2V_EINVAL, "t2v_attn_spatial: null pointer");
     T2V_REQUIRE(n_img > 0 && seq_q > 0 && seq_kv > 0 && heads > 0 && kv_div > 0, T2V_EINVAL, "t2v_attn_spatial: bad size");
     T2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ld_vt % 8 == 0 && ldo % 4 == 0, T2V_ESHAPE, "t2v_attn_spatial: strides");
+    T2V_REQUIRE(ldq >= heads * 64 && ldk >= heads * 64 && ldo >= heads * 64, T2V_ESHAPE, "t2v_attn_spatial: row stride smaller than heads * 64");
     T2V_REQUIRE(ld_vt >= ((seq_kv + 63) / 64) * 64, T2V_ESHAPE, "t2v_attn_spatial: V^T rows must be padded to 64 keys");
     T2V_REQUIRE(heads <= 65535 && n_img <= 65535, T2V_ESHAPE, "t2v_attn_spatial: grid");
     if (vt_img_stride <= 0) vt_img_stride = (long long)heads * 64 * ld_vt;
@@ -689,6 +690,8 @@ extern "C" int t2v_attn_temporal(const void* q, int ldq, const void* k, int ldk,
     T2V_REQUIRE(n_clips > 0 && frames > 0 && hw > 0 && heads > 0, T2V_EINVAL, "t2v_attn_temporal: bad size");
     T2V_REQUIRE(frames <= 1024, T2V_ESHAPE, "t2v_attn_temporal: more than 1024 frames not supported");
     T2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, T2V_ESHAPE, "t2v_attn_temporal: strides");
+    T2V_REQUIRE(ldq >= heads * 64 && ldk >= heads * 64 && ldv >= heads * 64 && ldo >= heads * 64, T2V_ESHAPE,
+                "t2v_attn_temporal: row stride smaller than heads * 64");
     const long long n_items = (long long)n_clips * hw * heads;
     const unsigned blocks = (unsigned)((n_items + 3) / 4);
     hipStream_t s = (hipStream_t)stream;

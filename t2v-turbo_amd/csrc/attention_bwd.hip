@@ -364,6 +364,8 @@ extern "C" int t2v_attn_spatial_bwd(const void* q, int ldq, const void* k, int l
     T2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ld_kt % 8 == 0 && ld_qt % 8 == 0 && ldo % 8 == 0 && ldoo % 8 == 0 &&
                 lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && v_img_stride % 8 == 0 && v_head_stride % 8 == 0, T2V_ESHAPE,
                 "t2v_attn_spatial_bwd: row strides");
+    T2V_REQUIRE(ldq >= heads * 64 && ldk >= heads * 64 && ldo >= heads * 64 && ldoo >= heads * 64 && lddq >= heads * 64 && lddk >= heads * 64 &&
+                lddv >= heads * 64 && ldv >= 64, T2V_ESHAPE, "t2v_attn_spatial_bwd: row stride smaller than the row");
     const bf16_t* zero = (const bf16_t*)t2v_zero_page();
     T2V_REQUIRE(zero, T2V_EHIP, "t2v_attn_spatial_bwd: zero page");
     hipStream_t s = (hipStream_t)stream;

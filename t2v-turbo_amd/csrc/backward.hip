@@ -226,6 +226,7 @@ extern "C" int t2v_gn_bwd(const void* x, int ldx, int C, int n_units, int rows_p
     T2V_REQUIRE(n_units > 0 && rows_per_unit > 0 && groups > 0 && groups <= 128, T2V_EINVAL, "t2v_gn_bwd: bad size");
     T2V_REQUIRE(C % 8 == 0 && C <= 2048 && C % groups == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && (!resid || ldr % 8 == 0),
                 T2V_ESHAPE, "t2v_gn_bwd: channels <= 2048, multiples of 8");
+    T2V_REQUIRE(C > 0 && ldx >= C && ldy >= C && ldo >= C && (!resid || ldr >= C), T2V_ESHAPE, "t2v_gn_bwd: row stride smaller than C");
     hipStream_t s = (hipStream_t)stream;
     const GbGeom gg = gb_geom(C);
     const int slab_rows = gb_slab_rows(C, rows_per_unit);

@@ -559,6 +559,8 @@ extern "C" int t2v_gn_bwd2(const void* x, int xc0, int ldx, const void* x1, int 
     const int C = xc0 + xc1;
     T2V_REQUIRE(xc0 % 8 == 0 && xc1 % 8 == 0 && C <= 4096 && C % groups == 0 && ldx % 8 == 0 && ldx1 % 8 == 0 && ldy % 8 == 0 &&
                 ldo % 8 == 0 && (!resid || ldr % 8 == 0), T2V_ESHAPE, "t2v_gn_bwd: channels <= 4096, multiples of 8");
+    T2V_REQUIRE(xc0 > 0 && xc1 >= 0 && ldx >= xc0 && (!x1 || ldx1 >= xc1) && ldy >= C && ldo >= C && (!resid || ldr >= C), T2V_ESHAPE,
+                "t2v_gn_bwd: row stride smaller than the channel count");
     hipStream_t s = (hipStream_t)stream;
     const Gb2Geom gg = gb2_geom(C);
     const int slab_rows = gb2_slab_rows(C, rows_per_unit);
@@ -586,6 +588,7 @@ extern "C" int t2v_layernorm_bwd(const void* x, int ldx, int M, int C, const flo
     T2V_REQUIRE(x && gamma && dy && dx && M > 0 && C > 0, T2V_EINVAL, "t2v_layernorm_bwd: bad argument");
     T2V_REQUIRE(C % 8 == 0 && C <= 2048 && ldx % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && (!resid || ldr % 8 == 0), T2V_ESHAPE,
                 "t2v_layernorm_bwd: C <= 2048, multiples of 8");
+    T2V_REQUIRE(ldx >= C && ldy >= C && ldo >= C && (!resid || ldr >= C), T2V_ESHAPE, "t2v_layernorm_bwd: row stride smaller than C");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((M + 3) / 4)), blk(256);
     const int nj = (C / 8 + 63) / 64;
@@ -633,6 +636,7 @@ extern "C" int t2v_add_bf16(const void* a, int lda, const void* b, int ldb, void
     T2V_REQUIRE(a && b && out && M > 0 && C > 0, T2V_EINVAL, "t2v_add_bf16: bad argument");
     T2V_REQUIRE(C % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldo % 8 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0 &&
                 (uintptr_t)out % 16 == 0, T2V_ESHAPE, "t2v_add_bf16: 16-byte aligned rows");
+    T2V_REQUIRE(lda >= C && ldb >= C && ldo >= C, T2V_ESHAPE, "t2v_add_bf16: row stride smaller than C");
     const long long work = M * (C / 8);
     hipLaunchKernelGGL(add_bf16_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda,
                        (const bf16_t*)b, ldb, (bf16_t*)out, ldo, M, C);
@@ -649,6 +653,8 @@ extern "C" int t2v_attn_temporal_bwd(const void* q, int ldq, const void* k, int 
     const long long total = (long long)n_clips * hw * heads;
     T2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && ldq2 % 4 == 0 && ldk2 % 4 == 0 && ldv2 % 4 == 0, T2V_ESHAPE,
                 "t2v_attn_temporal_bwd: row strides (16-byte fragment loads, 8-byte stores)");
+    T2V_REQUIRE(ldq >= heads * 64 && ldk >= heads * 64 && ldv >= heads * 64 && ldo >= heads * 64 && ldq2 >= heads * 64 && ldk2 >= heads * 64 &&
+                ldv2 >= heads * 64, T2V_ESHAPE, "t2v_attn_temporal_bwd: row stride smaller than heads * 64");
     static const bool valu = [] { const char* e = getenv("T2V_TATTN_BWD_VALU"); return e && e[0] == '1'; }();  // the first (VALU / LDS) form, kept for A/B runs
     if (!valu) {
         hipLaunchKernelGGL(attn_temporal_bwd_mfma_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q,

@@ -284,6 +284,7 @@ extern "C" int t2v_im2col_bf16(const void* x0, int c0, int ld0, const void* x1, 
     T2V_REQUIRE(c0 % 8 == 0 && c1 % 8 == 0 && ld0 % 8 == 0 && (c1 == 0 || ld1 % 8 == 0) && ldo % 8 == 0 && ldo >= taps * C &&
                     (uintptr_t)x0 % 16 == 0 && (uintptr_t)x1 % 16 == 0 && (uintptr_t)out % 16 == 0,
                 T2V_ESHAPE, "t2v_im2col_bf16: channels / row strides in multiples of 8, 16-byte aligned rows, ldo >= taps * C");
+    T2V_REQUIRE(ld0 >= c0 && (c1 == 0 || ld1 >= c1), T2V_ESHAPE, "t2v_im2col_bf16: row stride smaller than the part's channel count");
     T2V_REQUIRE(mode != T2V_GEMM_TCONV3 || (frames > 0 && n_img % frames == 0), T2V_ESHAPE, "t2v_im2col_bf16: n_img must be clips x frames");
     int ho = h, wo = w;
     if (mode == T2V_GEMM_CONV3X3_S2) { ho = (h - 1) / 2 + 1; wo = (w - 1) / 2 + 1; }
@@ -347,6 +348,8 @@ extern "C" int t2v_norm_affine_grad(const void* x0, int c0, int ld0, const void*
     if (kind == 0)
         T2V_REQUIRE(stats && groups > 0 && C % groups == 0 && rows_per_unit > 0 && rows % rows_per_unit == 0, T2V_ESHAPE,
                     "t2v_norm_affine_grad: GroupNorm statistics [rows / rows_per_unit][groups][2]");
+    T2V_REQUIRE(ldy >= C && (kind == 2 || (ld0 >= c0 && (c1 == 0 || ld1 >= c1))) && (!dgamma || ld_dgamma >= C) && (!dbeta || ld_dbeta >= C),
+                T2V_ESHAPE, "t2v_norm_affine_grad: row stride smaller than the channel count");
     const long long n_out = rows / sum_rows;
     T2V_REQUIRE(n_out <= 65535, T2V_ESHAPE, "t2v_norm_affine_grad: grid");
     const int nblk = affine_grad_blocks(sum_rows, n_out);

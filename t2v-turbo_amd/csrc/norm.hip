@@ -714,6 +714,7 @@ int gn_check(const void* x0, int c0, int ld0, const void* x1, int c1, int ld1, i
     const int C = c0 + c1;
     T2V_REQUIRE(c0 % 8 == 0 && c1 % 8 == 0 && ld0 % 8 == 0 && (c1 == 0 || ld1 % 8 == 0), T2V_ESHAPE,
                 "groupnorm: channels / strides must be multiples of 8");
+    T2V_REQUIRE(ld0 >= c0 && (c1 == 0 || ld1 >= c1), T2V_ESHAPE, "groupnorm: row stride smaller than the part's channel count");
     T2V_REQUIRE(C % groups == 0 && C / 8 <= 256 * GN_MAX_CPT, T2V_ESHAPE, "groupnorm: unsupported channel count");
     T2V_REQUIRE(groups <= 128, T2V_ESHAPE, "groupnorm: too many groups");
     return T2V_OK;
@@ -770,6 +771,7 @@ extern "C" int t2v_gn_apply(const void* x0, int c0, int ld0, const void* x1, int
     if (rc) return rc;
     T2V_REQUIRE(stats && gamma && beta && out && ldo % 8 == 0, T2V_EINVAL, "t2v_gn_apply: bad argument");
     if (!x1) { c1 = 0; ld1 = 0; }
+    T2V_REQUIRE(ldo >= c0 + c1, T2V_ESHAPE, "t2v_gn_apply: ldo smaller than the channel count");
     const int C = c0 + c1;
     hipLaunchKernelGGL(gn_apply_kernel<0>, dim3(gn_nslab(C, rows_per_unit, groups), n_units), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x0, c0, ld0, (const bf16_t*)x1, c1, ld1, rows_per_unit, groups, gn_slab_rows(C, rows_per_unit, groups),
@@ -948,6 +950,7 @@ extern "C" int t2v_group_norm(const void* x0, int c0, int ld0, const void* x1, i
     if (rc) return rc;
     T2V_REQUIRE(ws && gamma && beta && out && ldo % 8 == 0, T2V_EINVAL, "t2v_group_norm: bad argument");
     if (!x1) { c1 = 0; ld1 = 0; }
+    T2V_REQUIRE(ldo >= c0 + c1, T2V_ESHAPE, "t2v_group_norm: ldo smaller than the channel count");
     hipStream_t s = (hipStream_t)stream;
     if (const int nt = gn_group_threads(c0, c1, rows_per_unit, groups, prefetch_bytes)) {
         const float inv = 1.0f / ((float)rows_per_unit * (float)((c0 + c1) / groups));
@@ -1136,7 +1139,8 @@ extern "C" int t2v_gn_stats_cs(const float* cs0, int c0, const float* cs1, int c
 extern "C" int t2v_layernorm(const void* x, int ldx, int M, int C, const float* gamma, const float* beta, float eps,
                              void* out, int ldo, void* stream) {
     T2V_REQUIRE(x && gamma && beta && out && M > 0, T2V_EINVAL, "t2v_layernorm: bad argument");
-    T2V_REQUIRE(C % 8 == 0 && C <= 64 * 8 * LN_MAX && ldx % 8 == 0 && ldo % 8 == 0, T2V_ESHAPE, "t2v_layernorm: unsupported C");
+    T2V_REQUIRE(C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX && ldx % 8 == 0 && ldo % 8 == 0, T2V_ESHAPE, "t2v_layernorm: unsupported C");
+    T2V_REQUIRE(ldx >= C && ldo >= C, T2V_ESHAPE, "t2v_layernorm: row stride smaller than C");
     // row-group form where C / 8 chunks split evenly over 8 / 16 / 32 / 64 lanes with at most 5 chunks per lane (the UNet's 320 /
     // 640 / 1280 and every power-of-two width from 64); T2V_LN_ROWGROUP=0: the one-row-per-wave kernels (round 1-4) for A/B
     static const bool rowgroup = !(getenv("T2V_LN_ROWGROUP") && getenv("T2V_LN_ROWGROUP")[0] == '0');
