@@ -62,6 +62,33 @@ const char* t2v_last_error(void);
 #define T2V_ACT_GEGLU 1 /* out[m,j] = x*gelu(gate); W rows packed in 64-row groups [32 x | 32 gate]; out has N/2 cols */
 #define T2V_ACT_SILU 2
 
+/* Operand forms of the descriptor (t2v_gemm, t2v_conv_halo, t2v_linear_pr; what tests/gemm_form_cases.py holds the kernels to)
+ *  - Every operand may be a view into a larger buffer.  Row strides (elements): lda0 >= c0, lda1 >= c1, ldw >= K (conv_halo:
+ *    >= t2v_conv_halo_pack_cols), ldo >= n_out, ldr >= n_out, ld_rowvec >= n_out, ld_ln_out >= N, ld_lora_t >= 64 leaves,
+ *    ld_lora_u >= 64, ld_rowstat >= N / 16, lnf_ld >= 2 lnf_nblk (n_out = N, or N / 2 with GEGLU).  A shorter stride is an invalid
+ *    descriptor: every entry point that takes the descriptor — the *_supported / t2v_gemm_plan queries included — returns a negative
+ *    code and launches nothing.  lda0, lda1, ldw % 8 == 0 and a0, a1, w 16-byte aligned (checked).  out, residual, bias, rowvec need no
+ *    alignment: 16-byte aligned bases with ldo, ldr % 8 == 0, ld_rowvec % 4 == 0 and n_out % 4 == 0 select the vector store path, anything
+ *    else the element-wise one (same values; GEGLU, split-K and the fused epilogues exist on the vector path only).
+ *  - READ: columns [0, c0) / [0, c1) of the A rows the gather addresses; columns [0, K) of W rows [0, N); bias [0, N); rowvec rows
+ *    [0, ceil(M / rowvec_div)) x columns [0, n_out); residual rows [0, M) x columns [0, n_out); lnf_stats rows [0, M) x floats
+ *    [0, 2 lnf_nblk); lnf_s [0, N); lora_t rows [0, M) x columns [0, 64 leaves); lora_u rows [0, N) x columns [0, 64) — ALL 64: the
+ *    rank columns beyond the leaf's rank must hold zero; the conv_halo pack's columns [0, t2v_conv_halo_pack_cols) of rows [0, N): the
+ *    padding behind 9 C must hold zero.
+ *  - NOT READ (may hold anything, NaN included): the stride gaps of every operand; A rows >= M of a LINEAR launch and every source row a
+ *    padding tap would address — taps outside the (n_img, h, w) grid, in a TCONV3 launch outside the clip's frames, come from the
+ *    library's zero page, never from the neighbouring row / image / clip; W rows >= N (the tail of the last channel tile is the zero
+ *    page's); the tail of a weight row between K and ldw.
+ *  - WRITTEN: columns [0, n_out) of out rows [0, M) (per batch element: at its o_stride offset); ln_out likewise over N columns;
+ *    rowstat_out rows [0, M) x floats [0, N / 16); colstat_out [M / 32][N][2]; the first splits * batch * M * N floats of ws when K is
+ *    split.  Nothing else: not the stride gaps, not rows >= M, not the workspace behind those floats, not the workspace at all when the
+ *    launch runs in one split (t2v_gemm_plan tells).
+ *  - Rounding: the product is accumulated in fp32 over K in an unspecified order (split-K: fp32 partial sums added in split order).  The
+ *    epilogue is fp32 throughout — alpha * acc, + bias, GEGLU value * gelu(gate) (gate = alpha * acc + bias of the gate row; gelu =
+ *    csrc/gelu_poly.h, |error| < 4.2e-5 for |gate| <= 8), dropout mask and scale, + rowvec, + residual (also in t2v_conv_halo: the
+ *    residual meets the fp32 accumulator, not a rounded product), + the LoRA term, SiLU — and the result is rounded ONCE, to nearest
+ *    even, when it is stored as bf16 (not at all with out_f32).  rowstat_out and ln_out are taken from the fp32 epilogue values,
+ *    colstat_out from the bf16-rounded outputs.  ln_in / gn_coef (t2v_linear_pr) round the normalised A rows to bf16 before the product. */
 typedef struct t2v_gemm_desc {
     /* A: bf16 activations; optional second source = virtual channel concat [a0 | a1] */
     const void* a0;
@@ -244,7 +271,8 @@ int t2v_ffn_fused(const void* x, int ldx, int M, int C, const void* w1p, const f
 #endif
 
 /* direct 3x3 s1 p1 conv for tiny Cin (the 4-channel latent): x bf16 [M][cin] (cin <= 8),
- * w fp32 [cout][9][cin], bias fp32 [cout], out bf16 [M][cout].
+ * w fp32 [cout][9][cin], bias fp32 [cout], out bf16 [M][cout]; x and out are contiguous (no row strides), taps outside an image are zero
+ * (never the neighbouring row / image), fp32 accumulation, one rounding to bf16.
  * Replaces input_blocks.0 (openaimodel3d.py:435) and Decoder.conv_in (ae_modules.py:550-552). */
 int t2v_conv3x3_small_cin(const void* x, int n_img, int h, int w, int cin, const float* wgt,
                           const float* bias, int cout, void* out, void* stream);
@@ -516,7 +544,11 @@ int t2v_attn_spatial_bwd(const void* q, int ldq, const void* k, int ldk, const v
  * workgroups (splits = 0: library choice); fp32 partial tiles go through the caller's workspace ws (>= splits*R*C*4 bytes, the split
  * count shrinks to fit) and are added in a fixed order.  With ONE split — a product with enough output tiles to fill the chip, or an
  * output larger than the workspace — the tiles are written to `out` directly and ws is not touched.  Output tile 64 x 64, or
- * 128 x 128 where both extents reach 128 and pad to multiples of 128 within 10 % (T2V_WGRAD_TILE128=0: always 64 x 64). */
+ * 128 x 128 where both extents reach 128 and pad to multiples of 128 within 10 % (T2V_WGRAD_TILE128=0: always 64 x 64).
+ * lda >= R, ldb >= C, ldo >= C (checked; lda, ldb % 8 == 0 and a, b 16-byte aligned, out 4-byte aligned at any ldo).  Only rows [0, M) and
+ * columns [0, R) / [0, C) of the operands are read — the kernel contracts over tokens, so a row past M would reach every output — only
+ * columns [0, C) of out rows [0, R) and the first splits * R * C floats of ws are written; fp32 accumulation, alpha applied in fp32, a
+ * fixed summation order (two launches with the same arguments give the same bits).  The same holds per problem of t2v_wgrad_tn_group. */
 int t2v_wgrad_tn(const void* a, int lda, const void* b, int ldb, long long M, int R, int C, float alpha, float* out, int ldo, float* ws,
                  long long ws_bytes, int splits, void* stream);
 /* t2v_wgrad_tn_group: up to T2V_WGRAD_GROUP_MAX such products in one launch pair (main + fixed-order reduce): the weight gradients
@@ -567,7 +599,8 @@ int t2v_norm_affine_grad(const void* x0, int c0, int ld0, const void* x1, int c1
  *     kind 1   out[c][(taps - 1 - t) * N + n] = w[n][c][t]      the data-gradient pack: the same conv over dy with channels and filters
  *                                                               swapped and the taps mirrored, ldo >= taps * N
  * Full fine-tuning re-makes every pack per optimizer step IN PLACE (the recorded launch lists keep their pointers); this replaces
- * torch's permute / flip / cast chain for the conv leaves (70 % of the UNet's parameters). */
+ * torch's permute / flip / cast chain for the conv leaves (70 % of the UNet's parameters).  Pure data movement: every element is the
+ * round-to-nearest-even bf16 of one parameter; ldo below the pack row is refused, columns behind the pack row are not written. */
 int t2v_repack_conv_f32(const float* w, int N, int C, int taps, int kind, void* out, int ldo, void* stream);
 /* t2v_transpose_pad_bf16: out[b][c][r] = in[b][r][c] for r < rows and 0 for rows <= r < roundup(rows, 64) — the K-contiguous,
  * K-padded operand of the token-contracted weight-gradient GEMMs (dU = dy^T t, dD = G^T x) in one pass; 16-byte accesses on both
@@ -577,9 +610,11 @@ int t2v_transpose_pad_bf16(const void* in, int ld_in, int rows, int cols, void* 
 /* t2v_dropout_bf16: out[r][c] = keep(r, c) ? x[r][c] / (1 - p') : 0  (+ resid[r][c]) over rows x ncols bf16 (ncols even), p' = ((p * 2^32) >> 16) / 65536
  * (the probability the 16-bit mask really drops with: the scale keeps E[out] = x exactly), where
  * keep is a pure function of (*seed, site, i = r * ncols + c): word = splitmix64(seed + site * 0x9E3779B97F4A7C15 + (i >> 2) *
- * 0xD1B54A32D192ED03), element i keeps iff bits [16 (i & 3), +16) of the word >= (p * 2^32) >> 16 (p resolved to 2^-16).  The backward calls it again with the same (seed,
+ * 0xD1B54A32D192ED03) in 64-bit wrapping arithmetic, splitmix64 being the FINALISER alone (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+ * z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 — no increment of its own), element i keeps iff bits [16 (i & 3), +16) of the word >= (p * 2^32) >> 16 (p resolved to 2^-16).  The backward calls it again with the same (seed,
  * site) on the gradient.  seed: device pointer to one uint64 (a replayed launch list follows the step's seed).  In-place is
- * allowed (out == x).  Replaces nn.Dropout in LoraInjected*.forward (utils/lora.py:45-50,124-129) and TemporalConvBlock
+ * allowed (out == x).  ncols, ldx, ldr, ldo even, every stride >= ncols, 4-byte aligned bases (checked); only columns [0, ncols) of a row
+ * are read / written; the scale and the residual add are fp32, one rounding to bf16.  Replaces nn.Dropout in LoraInjected*.forward (utils/lora.py:45-50,124-129) and TemporalConvBlock
  * (openaimodel3d.py:280-297); the random stream is not torch's (train-mode parity is statistical). */
 int t2v_dropout_bf16(const void* x, int ldx, const void* resid, int ldr, void* out, int ldo, long long rows, int ncols, float p,
                      const void* seed, unsigned site, void* stream);

@@ -446,6 +446,12 @@ static int halo_prepare(const t2v_gemm_desc* dd, HaloParams& p, int& cfg) {
     p.d = *dd;
     t2v_gemm_desc& d = p.d;
     if (!d.a1) { d.c1 = 0; d.lda1 = 0; }
+    {   // row strides that do not cover their rows: an invalid descriptor (t2v_gemm refuses it too), not a launch to pass on
+        const int n_out = d.act == T2V_ACT_GEGLU ? d.N / 2 : d.N;
+        T2V_REQUIRE(d.lda0 >= d.c0 && d.lda1 >= d.c1, T2V_EINVAL, "t2v_conv_halo: lda0 < c0 or lda1 < c1");
+        T2V_REQUIRE(d.ldo >= n_out && (!d.residual || d.ldr >= n_out) && (!d.rowvec || d.ld_rowvec >= n_out), T2V_EINVAL,
+                    "t2v_conv_halo: ldo / ldr / ld_rowvec smaller than the output row");
+    }
     if (d.mode != T2V_GEMM_CONV3X3 && d.mode != T2V_GEMM_CONV3X3_UP2) return T2V_OK;
     p.ups = d.mode == T2V_GEMM_CONV3X3_UP2 ? 1 : 0;
     if (d.batch > 1 || d.alpha != 1.0f || d.out_f32 || d.split_k > 1 || d.drop_thr || d.ln_out || d.rowstat_out || d.lnf_stats || d.lora_t ||

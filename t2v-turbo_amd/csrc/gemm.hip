@@ -1390,6 +1390,11 @@ static int gemm_prepare(const t2v_gemm_desc* dd, GemmParams& p, int& cfg_out, in
     p.zero = t2v_zero_page();
     T2V_REQUIRE(p.zero, T2V_EHIP, "t2v_gemm: zero page allocation failed");
     const int n_out = d.act == T2V_ACT_GEGLU ? d.N / 2 : d.N;
+    // every row stride covers its row (a shorter one makes consecutive rows overlap: the launch would read / write its neighbours' columns)
+    T2V_REQUIRE(d.lda0 >= d.c0 && d.lda1 >= d.c1, T2V_EINVAL, "t2v_gemm: lda0 < c0 or lda1 < c1");
+    T2V_REQUIRE(d.ldo >= n_out && (!d.residual || d.ldr >= n_out), T2V_EINVAL, "t2v_gemm: ldo / ldr smaller than the output row");
+    T2V_REQUIRE(!d.rowvec || d.ld_rowvec >= n_out, T2V_EINVAL, "t2v_gemm: ld_rowvec smaller than the output row");
+    T2V_REQUIRE(!d.ln_out || d.ld_ln_out >= d.N, T2V_EINVAL, "t2v_gemm: ld_ln_out < N");
     p.vec4 = (d.ldo % 8 == 0) && (n_out % 4 == 0) && ((uintptr_t)d.out % 16 == 0) && (d.o_stride0 % 8 == 0) &&
              (d.o_stride1 % 8 == 0) && (!d.residual || (d.ldr % 8 == 0 && (uintptr_t)d.residual % 16 == 0)) &&
              (!d.bias || (uintptr_t)d.bias % 16 == 0) && (!d.rowvec || ((uintptr_t)d.rowvec % 16 == 0 && d.ld_rowvec % 4 == 0));

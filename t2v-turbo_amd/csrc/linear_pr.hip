@@ -494,6 +494,12 @@ static int lpr_prepare(const t2v_gemm_desc* dd, LprParams& p, int& cfg, int& til
     T2V_REQUIRE(dd && dd->a0 && dd->w && dd->out, T2V_EINVAL, "t2v_linear_pr: null pointer");
     p.d = *dd;
     const t2v_gemm_desc& d = p.d;
+    {   // row strides that do not cover their rows: an invalid descriptor (t2v_gemm refuses it too), not a launch to pass on
+        const int n_out = d.act == T2V_ACT_GEGLU ? d.N / 2 : d.N;
+        T2V_REQUIRE(d.lda0 >= d.c0 && (!d.a1 || d.lda1 >= d.c1), T2V_EINVAL, "t2v_linear_pr: lda0 < c0 or lda1 < c1");
+        T2V_REQUIRE(d.ldo >= n_out && (!d.residual || d.ldr >= n_out) && (!d.rowvec || d.ld_rowvec >= n_out), T2V_EINVAL,
+                    "t2v_linear_pr: ldo / ldr / ld_rowvec smaller than the output row");
+    }
     if (d.mode != T2V_GEMM_LINEAR || d.a1 || d.c1 || d.batch > 1 || d.alpha != 1.0f || d.out_f32 || d.split_k > 1 || d.drop_thr || d.ln_out ||
         d.rowstat_out || d.colstat_out || d.lnf_stats || d.lora_t || d.rowvec || (d.act != T2V_ACT_NONE && d.act != T2V_ACT_GEGLU))
         return T2V_OK;

@@ -294,6 +294,7 @@ __global__ __launch_bounds__(256) void wgrad_tn_group_reduce_kernel(const WgradG
 extern "C" int t2v_wgrad_tn(const void* a, int lda, const void* b, int ldb, long long M, int R, int C, float alpha, float* out, int ldo,
                             float* ws, long long ws_bytes, int splits, void* stream) {
     T2V_REQUIRE(a && b && out && ws && M > 0 && R > 0 && C > 0 && ldo >= C, T2V_EINVAL, "t2v_wgrad_tn: bad argument");
+    T2V_REQUIRE(lda >= R && ldb >= C, T2V_EINVAL, "t2v_wgrad_tn: lda < R or ldb < C");
     T2V_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0, T2V_ESHAPE,
                 "t2v_wgrad_tn: 16-byte aligned operand rows");
     const long long steps = (M + WT_TOK - 1) / WT_TOK;
@@ -353,6 +354,7 @@ extern "C" int t2v_wgrad_tn_group(const t2v_wgrad_problem* p, int n, float* ws, 
     for (int i = 0; i < n; ++i) {
         T2V_REQUIRE(p[i].a && p[i].b && p[i].out && p[i].M > 0 && p[i].R > 0 && p[i].C > 0 && p[i].ldo >= p[i].C, T2V_EINVAL,
                     "t2v_wgrad_tn_group: bad problem");
+        T2V_REQUIRE(p[i].lda >= p[i].R && p[i].ldb >= p[i].C, T2V_EINVAL, "t2v_wgrad_tn_group: lda < R or ldb < C");
         T2V_REQUIRE(p[i].lda % 8 == 0 && p[i].ldb % 8 == 0 && (uintptr_t)p[i].a % 16 == 0 && (uintptr_t)p[i].b % 16 == 0, T2V_ESHAPE,
                     "t2v_wgrad_tn_group: 16-byte aligned operand rows");
         total_tiles += (long long)((p[i].R + 63) / 64) * ((p[i].C + 63) / 64);

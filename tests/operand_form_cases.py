@@ -1037,5 +1037,6 @@ def report_lines():
     return [f"{c:44s} {t:22s} rounding {m:.2e}  bound {b:.2e}  observed {e:.2e}" for c, t, m, b, e in REPORT]
 
 
-def run_refusal(ops, dev, name):
-    dict(refusal_cases(ops, dev))[name]()
+def run_refusal(ops, dev, name, table=None):
+    """``table``: another module's refusal table of the same form (tests/gemm_form_cases.py)."""
+    dict((table or refusal_cases)(ops, dev))[name]()
