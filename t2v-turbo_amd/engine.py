@@ -393,6 +393,7 @@ def params_fingerprint(module, skip=()):
 class _Engine:
     def __init__(self, ops):
         self.ops = ops
+        self.native = getattr(ops, "is_native", False)   # launch lists are recorded and replayed; else (emulation, tests) the closures re-run
         self.adt = ops.act_dtype
         self.plans = {}
         self.fingerprint = None
@@ -439,7 +440,7 @@ class _Engine:
     def gn(self, x, norm, units, rows_per_unit, silu, eps=None, then=None):
         """GroupNorm(+SiLU) of an Act (possibly a virtual concat) -> new single-part tensor.  ``then``: the packed weight tensor
         of the launch that consumes the result (prefetched toward the Infinity Cache by the normalise pass)."""
-        pf = {"prefetch": then} if (then is not None and self.prefetch_weights and getattr(self.ops, "is_native", False)) else {}
+        pf = {"prefetch": then} if (then is not None and self.prefetch_weights and self.native) else {}
         ops = self.ops
         G = norm.num_groups
         eps = norm.eps if eps is None else eps
@@ -570,7 +571,7 @@ class _Engine:
     def ln_fusable(self, C, norm):
         """The 160x320 workgroup tile holds whole rows only at N = 320 (the full-resolution level: 60 of the 99 LayerNorms).  A
         non-native (emulated) backend takes the fused form at every width, so that the CPU suite covers the dataflow."""
-        wide_ok = C == 320 or not getattr(self.ops, "is_native", False)
+        wide_ok = C == 320 or not self.native
         return self.fuse_ln and wide_ok and tuple(norm.normalized_shape) == (C,) and norm.elementwise_affine
 
     def conv(self, x, mod, mode, *, frames=0, rowvec=None, rowvec_div=0, residual=None, out_dtype=None, w=None, bias="auto",
@@ -687,31 +688,128 @@ class _Engine:
             self.plans.clear()
             self.fingerprint = fp
 
-    def _run(self, plan):
+    # ---- plan lifecycle: record the launch lists once, then refresh the static inputs and replay ----------------------
+    # A plan is a plain dict: "static" (the input buffers the lists read), the outputs, and per list ("rec", and "rec_bwd" of a
+    # gradient plan) either the recorded launches [(fn, args, name)] or, on the emulated backend, the closure ("fn" / "fn_bwd").
+    def _record_lists(self, plan, *lists):
+        """``lists``: ("rec", fwd), or ("rec", fwd), ("rec_bwd", bwd).  Native backend: every closure runs once, its launches
+        recorded into plan[key].  Emulated backend (tests): the closures themselves are the plan and only the first runs now —
+        every forward is followed by one backward."""
         ops = self.ops
-        if not getattr(ops, "is_native", False):
-            plan["fn"]()
+        if self.native:
+            ops.init()
+            for key, fn in lists:
+                ops.recording = []
+                try:
+                    fn()
+                finally:
+                    plan[key] = ops.recording
+                    ops.recording = None
+        else:
+            for key, fn in lists:
+                plan["fn" + key[3:]] = fn
+            lists[0][1]()
+        plan["pool_bytes"] = self.pool.bytes
+        return plan
+
+    def _adopt(self, key, plan):
+        """A freshly recorded plan becomes the engine's most recently used one; it holds the results of the call that recorded it."""
+        self._keep_plan(key, self._own(plan))
+        if self.native and "rec_bwd" in plan:
+            # recording executed the backward list once (on a zero gradient) and that recycled the saved forward
+            # buffers: run the forward list again so the tape holds this call's activations
+            self._replay(plan, "rec")
+        return plan
+
+    def _lookup_or_record(self, key, record, refresh):
+        """The plan of ``key`` after this call's forward: recorded now (``record()``; recording runs the launches), or its static
+        inputs refreshed (``refresh(plan["static"])``) and its forward list replayed."""
+        plan = self.plans.get(key)
+        if plan is None:
+            return self._adopt(key, record())
+        refresh(plan["static"])
+        self._replay(plan, "rec")
+        return plan
+
+    @staticmethod
+    def _once_per_forward(plan, what):
+        """The backward consumes what its forward saved: one backward per forward."""
+        if plan.get("bwd_id") == plan["fwd_id"]:
+            raise RuntimeError(f"{what}: backward was already run for this forward (its saved activations are gone)")
+        plan["bwd_id"] = plan["fwd_id"]
+
+    @staticmethod
+    def _capture(issue, device=None):
+        """The launches ``issue()`` makes on the current stream, captured into a new hipGraph (not yet replayed)."""
+        torch.cuda.synchronize(device)
+        g = torch.cuda.CUDAGraph()
+        # (thread-local capture mode: a HIP call from ANOTHER thread — the watchdog of an RCCL process group polling its events while
+        # this thread captures — neither invalidates the capture nor faults in that thread; in the default global mode it invalidates
+        # the capture and aborts the watchdog: found as a once-in-five-runs abort of the one-rank RCCL test)
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            issue()
+        return g
+
+    def _replay(self, plan, which):
+        """Replay one recorded launch list of ``plan`` ("rec", or "rec_bwd" of a gradient plan); with ``use_graph`` (T2V_HIP_GRAPH=1)
+        each list is captured into its own hipGraph after its first plain replay (thousands of launches per list: the Python /
+        ctypes loop would otherwise set the pace).  Everything that changes between calls lives in static device buffers
+        (inputs, LoRA operand packs, seed)."""
+        ops = self.ops
+        if not self.native:
+            plan["fn" + which[3:]]()
             return
-        if self.use_graph and plan.get("graph") is not None:   # (use_graph switched off again: back to the plain loop)
-            plan["graph"].replay()
-            return
-        if self.use_graph and plan["runs"] >= 1 and not plan.get("graph_failed"):
+        # (the one list of an inference plan: plan["graph"]; the two of a gradient plan: plan["graph_rec"], plan["graph_rec_bwd"])
+        gkey, rkey = ("graph_" + which if "rec_bwd" in plan else "graph"), "runs_" + which
+        if self.use_graph and plan.get(gkey) is None and plan.get(rkey, 0) >= 1 and not plan.get("graph_failed"):
             try:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                # (thread-local capture mode: a HIP call from ANOTHER thread — the watchdog of an RCCL process group polling its events —
-                # neither invalidates the capture nor faults in that thread; found as a once-in-five-runs abort of the one-rank RCCL test)
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    ops.replay(plan["rec"], ops.stream())
-                plan["graph"] = g
-                g.replay()
-                return
+                # a list is cut at its host-side entries (the gradient exchange's segment markers): one hipGraph per run of
+                # launches, the host calls re-issued between the graph launches
+                built = []
+                for launches, host in cut_at_host_calls(plan[which]):
+                    if launches is None:
+                        built.append((None, host))
+                    else:   # (a cut piece is a temporary sub-list: nothing to reuse; the whole list keeps its compiled program)
+                        whole = launches is plan[which]
+                        built.append((self._capture(lambda: ops.replay(launches, ops.stream(), cache=whole)), None))
+                plan[gkey] = built
             except Exception as e:  # capture unsupported -> stay on plain replay, loudly
                 plan["graph_failed"] = str(e)
                 import warnings
-                warnings.warn(f"hipGraph capture failed, replaying launches instead: {e}")
-        ops.replay(plan["rec"], ops.stream())
-        plan["runs"] += 1
+                warnings.warn(f"hipGraph capture of the {which} list failed, replaying launches instead: {e}")
+        if self.use_graph and plan.get(gkey) is not None:   # (use_graph switched off again: back to the plain loop)
+            for g, host in plan[gkey]:      # graphs of the launch runs, host calls (all-reduce markers) between them
+                if g is not None:
+                    g.replay()
+                else:
+                    host[0](*host[1], None)
+            return
+        ops.replay(plan[which], ops.stream())
+        plan[rkey] = plan.get(rkey, 0) + 1
+
+
+# the entries of a recorded list that are host calls (``HipOps.record_host_call``: engine_lora's gradient exchange markers), by name
+HOST_CALL = "allreduce_segment"
+
+
+def cut_at_host_calls(rec):
+    """A recorded list [(fn, args, name)] cut at its host-side entries -> [(launches, None) | (None, (fn, args))] in list order: runs
+    of launches and the host calls between them, no run empty.  A list without a host entry is ONE run, and that run is the
+    list object itself (``HipOps.replay`` keeps a compiled program per list object)."""
+    if not any(e[2] == HOST_CALL for e in rec):
+        return [(rec, None)] if rec else []
+    runs, cur = [], []
+    for e in rec:
+        if e[2] == HOST_CALL:
+            if cur:
+                runs.append((cur, None))
+                cur = []
+            runs.append((None, (e[0], e[1])))
+        else:
+            cur.append(e)
+    if cur:
+        runs.append((cur, None))
+    return runs
 
 
 # =================================================================================== UNet
@@ -742,28 +840,17 @@ class UNetEngine(_Engine):
         drops = self._active_tconv_dropouts() if (m.training or self._any_live_dropout()) else {}
         if plan is None or plan["training"] != m.training or plan.get("drop_sig") != tuple(sorted(drops.values())):
             self.drop_ps = drops   # id(nn.Dropout) -> p of the TemporalConvBlock dropouts that are live (train-mode frozen network)
-            plan = self._own(self._record(x, timesteps, context, fps, timestep_cond, motion_cond))
+            plan = self._record(x, timesteps, context, fps, timestep_cond, motion_cond)
             plan["training"] = m.training
             plan["drop_sig"] = tuple(sorted(drops.values()))
-            self._keep_plan(key, plan)
+            self._adopt(key, plan)
         else:
             self._keep_plan(key, plan)
             st = plan["static"]
             if "seed" in st:   # a fresh mask per call (the launch list reads the seed from device memory: replays follow it)
                 st["seed"].fill_(self._next_seed())
-            st["x"].copy_(x)
-            st["ts"].copy_(timesteps)
-            st["ctx"].copy_(context)
-            if m.fps_cond:
-                if fps_is_int:
-                    st["fps"].fill_(fps)
-                else:
-                    st["fps"].copy_(fps)
-            if timestep_cond is not None:
-                st["tc"].copy_(timestep_cond)
-            if motion_cond is not None:
-                st["mc"].copy_(motion_cond)
-            self._run(plan)
+            self._load_inputs(st, x, timesteps, context, fps, timestep_cond, motion_cond)
+            self._replay(plan, "rec")
         self._publish_probs(plan)
         return plan["out"].clone()
 
@@ -816,41 +903,41 @@ class UNetEngine(_Engine):
 
     # ---- recording ----------------------------------------------------------------------------------------
     def _record(self, x, timesteps, context, fps, timestep_cond, motion_cond):
-        m, ops = self.model, self.ops
+        m = self.model
         self._begin(x.device)
         B, Cin, F, H, W = x.shape
         self.B, self.F = B, F
+        st = self._static_inputs(x, timesteps, context, fps, timestep_cond, motion_cond)
+        if getattr(self, "drop_ps", None):
+            st["seed"] = torch.full((1,), self._next_seed(), dtype=torch.int64, device=x.device)
+        self.seed_t = st.get("seed")
+        out = torch.empty_like(st["x"][:, :m.out_channels].contiguous()) if m.out_channels != Cin else torch.empty_like(st["x"])
+        plan = {"static": st, "out": out, "probs": []}
+        self.plan = plan
+        return self._record_lists(plan, ("rec", lambda: self._forward(st, out)))
+
+    # ---- the static inputs every UNet launch list reads (the gradient engine adds "dout", "emb_all", "seed") ----------------
+    def _static_inputs(self, x, timesteps, context, fps, timestep_cond, motion_cond):
         st = {"x": x.detach().clone().contiguous(), "ts": timesteps.detach().to(torch.int64).clone(),
               "ctx": context.detach().clone().contiguous()}
-        if m.fps_cond:
+        if self.model.fps_cond:
             st["fps"] = (torch.full_like(st["ts"], fps) if isinstance(fps, int) else fps.detach().to(torch.int64).clone())
         if timestep_cond is not None:
             st["tc"] = timestep_cond.detach().clone().contiguous()
         if motion_cond is not None:
             st["mc"] = motion_cond.detach().clone().contiguous()
-        if getattr(self, "drop_ps", None):
-            st["seed"] = torch.full((1,), self._next_seed(), dtype=torch.int64, device=x.device)
-        self.seed_t = st.get("seed")
-        out = torch.empty_like(st["x"][:, :m.out_channels].contiguous()) if m.out_channels != Cin else torch.empty_like(st["x"])
-        plan = {"static": st, "out": out, "probs": [], "runs": 0}
-        self.plan = plan
+        return st
 
-        def body():
-            self._forward(st, out)
-
-        if getattr(ops, "is_native", False):
-            ops.init()
-            ops.recording = []
-            try:
-                body()
-            finally:
-                plan["rec"] = ops.recording
-                ops.recording = None
-        else:
-            plan["fn"] = body
-            body()
-        plan["pool_bytes"] = self.pool.bytes
-        return plan
+    def _load_inputs(self, st, x, timesteps, context, fps, timestep_cond, motion_cond):
+        st["x"].copy_(x)
+        st["ts"].copy_(timesteps)
+        st["ctx"].copy_(context)
+        if self.model.fps_cond:
+            st["fps"].fill_(fps) if isinstance(fps, int) else st["fps"].copy_(fps)
+        if timestep_cond is not None:
+            st["tc"].copy_(timestep_cond)
+        if motion_cond is not None:
+            st["mc"].copy_(motion_cond)
 
     def _forward(self, st, out):
         m, ops, pk = self.model, self.ops, self.pk
@@ -858,8 +945,45 @@ class UNetEngine(_Engine):
         self.drop_sites = []   # ([nn.Dropout], kind, geometry) per applied mask, in launch order (tests replay them inside the torch module)
         x = st["x"]
         _, Cin, _, H, W = x.shape
-        mc = m.model_channels
-        L, D = st["ctx"].shape[1], st["ctx"].shape[2]
+        self._embedding(st)
+        self._context(st)
+        # ---- input conv on the 4-channel latent -----------------------------------------------------------------
+        xt = self.buf(B * F * H * W, Cin)
+        ops.ncfhw_to_tokens(x, xt)
+        conv_in = m.input_blocks[0][0]
+        h0 = self.buf(B * F * H * W, leaf_out_channels(conv_in))
+        ops.conv_small(xt, B * F, H, W, pk.small_conv(conv_in), pk.bias(conv_in), h0)
+        h = Act(h0, B * F, H, W)
+        hs = []
+        for i, block in enumerate(m.input_blocks):
+            if i > 0:
+                h = self.run_sequential(block, h)
+            if i == 0 and m.addition_attention:
+                h = self.run_sequential(m.init_attn, h)
+            hs.append(h)
+        h = self.run_sequential(m.middle_block, h)
+        for block in m.output_blocks:
+            skip = hs.pop()
+            h = self.run_sequential(block, Act([h.t, skip.t], h.n_img, h.h, h.w, cs=[h.cs[0], skip.cs[0]]), release=[h.t, skip.t])
+        # ---- out: GroupNorm -> SiLU -> conv to 4 channels, fp32, back to (b c f h w) ------------------------------
+        t = self.gn(h, m.out[0], B * F, H * W, True, then=self.pk.conv(m.out[2]))
+        y = self.conv(Act(t, h.n_img, h.h, h.w), m.out[2], nt.GEMM_CONV3X3, out_dtype=torch.float32)
+        ops.tokens_to_ncfhw(y.t, out)
+
+    # ---- conditioning prelude: no dependence on the latents -------------------------------------------------------------
+    def _emb_table(self, cls=ResBlock):
+        """``emb_off``: the column offset of every residual block's slice of ``emb_all`` -> (the blocks, total width)."""
+        blocks = [mod for mod in self.model.modules() if isinstance(mod, cls)]
+        self.emb_off, off = {}, 0
+        for rb in blocks:
+            self.emb_off[id(rb)] = off
+            off += rb.out_channels
+        return blocks, off
+
+    def _embedding(self, st):
+        """Timestep (+ timestep_cond, motion_cond), fps embeddings -> ``self.emb_all`` [B, sum of ResBlock widths] fp32."""
+        m, ops, pk = self.model, self.ops, self.pk
+        B, mc = self.B, m.model_channels
         # ---- conditioning vectors (M = B rows; openaimodel3d.py:683-706) ----------------------------------
         t_emb = self.buf(B, mc)
         ops.timestep_embedding(st["ts"], mc, False, t_emb)
@@ -886,43 +1010,19 @@ class UNetEngine(_Engine):
         emb_s = self.buf(B, emb.shape[1])
         ops.silu(emb, emb_s)
         # every ResBlock's emb_layers Linear in one GEMM (rows are identical across frames: K17)
-        resblocks = [mod for mod in m.modules() if isinstance(mod, ResBlock)]
-        self.emb_off, off = {}, 0
-        for rb in resblocks:
-            self.emb_off[id(rb)] = off
-            off += rb.out_channels
-        lins = [rb.emb_layers[1] for rb in resblocks]
+        lins = [rb.emb_layers[1] for rb in self._emb_table()[0]]
         w_all = pk.cat_mats(lins, "emb_all")
         b_all = pk._memo(("emb_all_bias",) + tuple(id(l) for l in lins),
                          lambda: torch.cat([pk.bias(l) for l in lins]).contiguous())
         self.emb_all = self.linear(emb_s, None, w=w_all, bias=b_all, out_dtype=torch.float32)
-        # ---- context in activation dtype, shared by all frames of a clip (K11) ----------------------------
-        self.ctx = self.buf(B * L, D)
-        ops.cast(st["ctx"], self.ctx)
+
+    def _context(self, st):
+        """Context in activation dtype, shared by all frames of a clip (K11); the per-layer K / V caches start empty."""
+        L, D = st["ctx"].shape[1], st["ctx"].shape[2]
+        self.ctx = self.buf(self.B * L, D)
+        self.ops.cast(st["ctx"], self.ctx)
         self.ctx_len = L
         self.ctx_kv = {}
-        # ---- input conv on the 4-channel latent -----------------------------------------------------------------
-        xt = self.buf(B * F * H * W, Cin)
-        ops.ncfhw_to_tokens(x, xt)
-        conv_in = m.input_blocks[0][0]
-        h0 = self.buf(B * F * H * W, leaf_out_channels(conv_in))
-        ops.conv_small(xt, B * F, H, W, pk.small_conv(conv_in), pk.bias(conv_in), h0)
-        h = Act(h0, B * F, H, W)
-        hs = []
-        for i, block in enumerate(m.input_blocks):
-            if i > 0:
-                h = self.run_sequential(block, h)
-            if i == 0 and m.addition_attention:
-                h = self.run_sequential(m.init_attn, h)
-            hs.append(h)
-        h = self.run_sequential(m.middle_block, h)
-        for block in m.output_blocks:
-            skip = hs.pop()
-            h = self.run_sequential(block, Act([h.t, skip.t], h.n_img, h.h, h.w, cs=[h.cs[0], skip.cs[0]]), release=[h.t, skip.t])
-        # ---- out: GroupNorm -> SiLU -> conv to 4 channels, fp32, back to (b c f h w) ------------------------------
-        t = self.gn(h, m.out[0], B * F, H * W, True, then=self.pk.conv(m.out[2]))
-        y = self.conv(Act(t, h.n_img, h.h, h.w), m.out[2], nt.GEMM_CONV3X3, out_dtype=torch.float32)
-        ops.tokens_to_ncfhw(y.t, out)
 
     def run_sequential(self, seq, h, release=()):
         assert isinstance(seq, TimestepEmbedSequential)

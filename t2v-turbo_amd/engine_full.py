@@ -138,7 +138,7 @@ class FullTrainMixin:
         pk = plan["owned"][1]
         assert pk is self.pk, "the pack refresh runs on the Packer of the plan being replayed (full_activate)"
         dev = getattr(self, "device", None)
-        if not (self.refresh_graph and getattr(self.ops, "is_native", False) and dev is not None and dev.type == "cuda"):
+        if not (self.refresh_graph and self.native and dev is not None and dev.type == "cuda"):
             pk.refresh(self.ops)
             return
         from .nn_util import walk_parameters
@@ -155,10 +155,7 @@ class FullTrainMixin:
             pk.refresh(self.ops)
             return
         try:                                         # second pass: capture, then run the captured pass
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize(dev)
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                pk.refresh(self.ops)
+            g = self._capture(lambda: pk.refresh(self.ops), dev)
             g.replay()
             st["graph"] = g
         except Exception as e:  # noqa: BLE001 - a maker the capture cannot take (host read-back, pageable copy): stay eager, say so once

@@ -19,7 +19,6 @@ class MSUNetEngine(UNetEngine):
         x = st["x"]
         _, Cin, _, H, W = x.shape
         mc = m.model_channels
-        L, D = st["ctx"].shape[1], st["ctx"].shape[2]
         te = m.time_embedding
         # ---- time embedding (unet_3d_condition.py:396-408): cos||sin -> (+ cond_proj(w)) -> linear_1 -> SiLU -> linear_2
         t_emb = self.buf(B, mc)
@@ -35,21 +34,13 @@ class MSUNetEngine(UNetEngine):
         emb = self.linear(e1, te.linear_2)
         emb_s = self.buf(B, emb.shape[1])
         ops.silu(emb, emb_s)
-        resnets = [mod for mod in m.modules() if isinstance(mod, ResnetBlock2D)]
-        self.emb_off, off = {}, 0
-        for rb in resnets:
-            self.emb_off[id(rb)] = off
-            off += rb.out_channels
-        lins = [rb.time_emb_proj for rb in resnets]
+        lins = [rb.time_emb_proj for rb in self._emb_table(ResnetBlock2D)[0]]
         w_all = pk.cat_mats(lins, "ms_emb_all")
         b_all = pk._memo(("ms_emb_all_bias",) + tuple(id(l) for l in lins),
                          lambda: torch.cat([pk.bias(l) for l in lins]).contiguous())
         self.emb_all = self.linear(emb_s, None, w=w_all, bias=b_all, out_dtype=torch.float32)
         # ---- text context, shared by all frames of a clip
-        self.ctx = self.buf(B * L, D)
-        ops.cast(st["ctx"], self.ctx)
-        self.ctx_len = L
-        self.ctx_kv = {}
+        self._context(st)
         # ---- conv_in on the 4-channel latent, then the input temporal transformer
         xt = self.buf(B * F * H * W, Cin)
         ops.ncfhw_to_tokens(x, xt)

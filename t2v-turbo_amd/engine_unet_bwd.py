@@ -127,21 +127,10 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                 # the LoRA operand / gradient arenas (engine_lora._lora_begin) are per engine, not per plan: a new input signature
                 # replaces the recorded plan instead of leaving one behind whose launches point into freed arenas
                 self.plans.clear()
-            plan = self._own(self._record_grad(x, timesteps, context, fps, timestep_cond, motion_cond, emb_all))
-            self._keep_plan(key, plan)
-            if getattr(self.ops, "is_native", False):
-                self._replay(plan, "rec")  # recording ran the backward once and recycled the saved buffers
+            plan = self._adopt(key, self._record_grad(x, timesteps, context, fps, timestep_cond, motion_cond, emb_all))
         else:
             st = plan["static"]
-            st["x"].copy_(x)
-            st["ts"].copy_(timesteps)
-            st["ctx"].copy_(context)
-            if m.fps_cond:
-                st["fps"].fill_(fps) if isinstance(fps, int) else st["fps"].copy_(fps)
-            if timestep_cond is not None:
-                st["tc"].copy_(timestep_cond)
-            if motion_cond is not None:
-                st["mc"].copy_(motion_cond)
+            self._load_inputs(st, x, timesteps, context, fps, timestep_cond, motion_cond)
             if emb_all is not None:
                 st["emb_all"].copy_(emb_all.detach())
                 if self.training_lora:
@@ -173,9 +162,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         if plan["out"].is_cuda and plan["out"].device.index != torch.cuda.current_device():
             with torch.cuda.device(plan["out"].device):
                 return self.backward(dout, dprobs, flat_grad, accumulate, grad_sync)
-        if plan.get("bwd_id") == plan["fwd_id"]:
-            raise RuntimeError("UNet gradient: backward was already run for this forward (its saved activations are gone)")
-        plan["bwd_id"] = plan["fwd_id"]
+        self._once_per_forward(plan, "UNet gradient")
         if self.training_full:
             self.full_activate(plan)              # (another signature's forward may have run since this plan's)
         st = plan["static"]
@@ -224,76 +211,16 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             return 0
         return world
 
-    def _replay(self, plan, which):
-        """Replay one of the two recorded launch lists; with ``use_graph`` (T2V_HIP_GRAPH=1) each list is captured into its own
-        hipGraph after its first plain replay (thousands of launches per list: the Python / ctypes loop would otherwise set
-        the pace).  Everything that changes between steps lives in static device buffers (inputs, LoRA operand packs, seed)."""
-        ops = self.ops
-        if not getattr(ops, "is_native", False):
-            plan["fn" if which == "rec" else "fn_bwd"]()
-            return
-        gkey, rkey = "graph_" + which, "runs_" + which
-        if self.use_graph and plan.get(gkey) is not None:
-            for g, host in plan[gkey]:      # graphs of the launch runs, host calls (all-reduce markers) between them
-                if g is not None:
-                    g.replay()
-                else:
-                    host[0](*host[1], None)
-            return
-        if self.use_graph and plan.get(rkey, 0) >= 1 and not plan.get("graph_failed") and plan.get(gkey) is None:
-            try:
-                # a list is cut at its host-side entries (the gradient exchange's segment markers): one hipGraph per run of
-                # launches, the host calls re-issued between the graph launches
-                runs, cur = [], []
-                for e in plan[which]:
-                    if e[2] == "allreduce_segment":
-                        if cur:
-                            runs.append((cur, None))
-                            cur = []
-                        runs.append((None, (e[0], e[1])))
-                    else:
-                        cur.append(e)
-                if cur:
-                    runs.append((cur, None))
-                built = []
-                torch.cuda.synchronize()
-                for launches, host in runs:
-                    if launches is None:
-                        built.append((None, host))
-                        continue
-                    g = torch.cuda.CUDAGraph()
-                    # (thread-local capture mode: the watchdog thread of an RCCL process group may poll its events while this thread
-                    # captures — in the default global mode that invalidates the capture and aborts the watchdog)
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        ops.replay(launches, ops.stream(), cache=False)   # (a temporary sub-list: nothing to reuse)
-                    built.append((g, None))
-                plan[gkey] = built
-                return self._replay(plan, which)
-            except Exception as e:  # capture unsupported -> stay on plain replay, loudly
-                plan["graph_failed"] = str(e)
-                import warnings
-                warnings.warn(f"hipGraph capture of the {which} list failed, replaying launches instead: {e}")
-        ops.replay(plan[which], ops.stream())
-        plan[rkey] = plan.get(rkey, 0) + 1
-
     # ---- recording ------------------------------------------------------------------------------------------------
     def _record_grad(self, x, timesteps, context, fps, timestep_cond, motion_cond, emb_all=None):
-        m, ops = self.model, self.ops
-        native = getattr(ops, "is_native", False)
+        m = self.model
         self._begin(x.device)
         B, Cin, F, H, W = x.shape
         self.B, self.F = B, F
-        st = {"x": x.detach().clone().contiguous(), "ts": timesteps.detach().to(torch.int64).clone(),
-              "ctx": context.detach().clone().contiguous()}
-        if m.fps_cond:
-            st["fps"] = (torch.full_like(st["ts"], fps) if isinstance(fps, int) else fps.detach().to(torch.int64).clone())
-        if timestep_cond is not None:
-            st["tc"] = timestep_cond.detach().clone().contiguous()
-        if motion_cond is not None:
-            st["mc"] = motion_cond.detach().clone().contiguous()
+        st = self._static_inputs(x, timesteps, context, fps, timestep_cond, motion_cond)
         out = torch.empty(B, m.out_channels, F, H, W, dtype=x.dtype, device=x.device)
         st["dout"] = torch.zeros_like(out)
-        plan = {"static": st, "out": out, "dx": torch.empty_like(st["x"]), "probs": [], "dprobs": {}, "runs": 0}
+        plan = {"static": st, "out": out, "dx": torch.empty_like(st["x"]), "probs": [], "dprobs": {}}
         if self.training_lora:
             # frozen base weights are packed as they are; the LoRA branch runs as its own GEMMs on per-step operand packs
             self.pk = Packer(self.adt, x.device, merge_lora=False)
@@ -328,20 +255,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         def bwd():
             self._backward_tape(st["dout"], plan["dx"])
 
-        if native:
-            ops.init()
-            for which, fn in (("rec", fwd), ("rec_bwd", bwd)):
-                ops.recording = []
-                try:
-                    fn()
-                finally:
-                    plan[which] = ops.recording
-                    ops.recording = None
-        else:  # emulation backend (tests): the closures themselves are the plan; every forward is followed by one backward
-            fwd()
-            plan["fn"], plan["fn_bwd"] = fwd, bwd
-        plan["pool_bytes"] = self.pool.bytes
-        return plan
+        return self._record_lists(plan, ("rec", fwd), ("rec_bwd", bwd))
 
     # ---- saved-activation bookkeeping: a tensor may be kept by several backward closures (skip connections) ----------
     def hold(self, *ts):
@@ -672,53 +586,14 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
 
     def _conditioning(self, st):
         """Embedding / context branch of UNetEngine._forward (no dependence on the latents: no tape)."""
-        m, ops, pk = self.model, self.ops, self.pk
-        B = self.B
-        mc = m.model_channels
-        L, D = st["ctx"].shape[1], st["ctx"].shape[2]
-        resblocks = [mod for mod in m.modules() if isinstance(mod, ResBlock)]
-        self.emb_off, off = {}, 0
-        for rb in resblocks:
-            self.emb_off[id(rb)] = off
-            off += rb.out_channels
-        self.ctx = self.buf(B * L, D)
-        ops.cast(st["ctx"], self.ctx)
-        self.ctx_len = L
-        self.ctx_kv = {}
+        self._context(st)
         self._ctx_f = None
         if self.trains:  # the M = B-row branch belongs to torch autograd (engine_lora.py / engine_full.py); its result is an input
-            assert st["emb_all"].shape == (B, off)
+            width = self._emb_table()[1]
+            assert st["emb_all"].shape == (self.B, width)
             self.emb_all = st["emb_all"]
-            return
-        t_emb = self.buf(B, mc)
-        ops.timestep_embedding(st["ts"], mc, False, t_emb)
-        emb_in = t_emb
-        if "tc" in st:
-            tcb = self.buf(B, st["tc"].shape[1])
-            ops.cast(st["tc"], tcb)
-            if "mc" in st:
-                cond = self.linear(tcb, m.time_cond_proj)
-                mcb = self.buf(B, st["mc"].shape[1])
-                ops.cast(st["mc"], mcb)
-                mproj = self.linear(mcb, m.motion_cond_proj)
-                emb_in = self.buf(B, mc)
-                ops.gemm(cond, pk.mat(m.combine_proj), emb_in, M=B, N=mc, a1=mproj, residual=t_emb)
-            else:
-                emb_in = self.linear(tcb, m.time_cond_proj, residual=t_emb)
-        e1 = self.linear(emb_in, m.time_embed[0], act=nt.ACT_SILU)
-        emb = self.linear(e1, m.time_embed[2])
-        if m.fps_cond:
-            f_emb = self.buf(B, mc)
-            ops.timestep_embedding(st["fps"], mc, False, f_emb)
-            f1 = self.linear(f_emb, m.fps_embedding[0], act=nt.ACT_SILU)
-            emb = self.linear(f1, m.fps_embedding[2], residual=emb)
-        emb_s = self.buf(B, emb.shape[1])
-        ops.silu(emb, emb_s)
-        lins = [rb.emb_layers[1] for rb in resblocks]
-        w_all = pk.cat_mats(lins, "emb_all")
-        b_all = pk._memo(("emb_all_bias",) + tuple(id(l) for l in lins),
-                         lambda: torch.cat([pk.bias(l) for l in lins]).contiguous())
-        self.emb_all = self.linear(emb_s, None, w=w_all, bias=b_all, out_dtype=torch.float32)
+        else:
+            self._embedding(st)
 
     def context_kv_t(self, attn, per_frame=False):
         """Training: K / V of ONE cross-attention layer through its own injected to_k / to_v (token-major rows of the text

@@ -44,41 +44,17 @@ class VAEDecodeEngine(_Engine):
         assert z.dim() == 5
         self._check_weights(self.vae)
         key = (tuple(z.shape), z.dtype, float(scale), z.device)
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = self._own(self._record(z, scale))
-            self._keep_plan(key, plan)
-        else:
-            plan["static"]["z"].copy_(z)
-            self._run(plan)
+        plan = self._lookup_or_record(key, lambda: self._record(z, scale), lambda st: st["z"].copy_(z))
         return plan["out"].clone()
 
     def _record(self, z, scale):
-        ops = self.ops
         self._begin(z.device)
         dec = self.vae.decoder
         b, zc, t, h, w = z.shape
         up = 2 ** (dec.num_resolutions - 1)
         st = {"z": z.detach().clone().contiguous()}
         out = torch.empty(b, leaf_out_channels(dec.conv_out), t, h * up, w * up, dtype=z.dtype, device=z.device)
-        plan = {"static": st, "out": out, "runs": 0}
-
-        def body():
-            self._forward(st["z"], scale, out)
-
-        if getattr(ops, "is_native", False):
-            ops.init()
-            ops.recording = []
-            try:
-                body()
-            finally:
-                plan["rec"] = ops.recording
-                ops.recording = None
-        else:
-            plan["fn"] = body
-            body()
-        plan["pool_bytes"] = self.pool.bytes
-        return plan
+        return self._record_lists({"static": st, "out": out}, ("rec", lambda: self._forward(st["z"], scale, out)))
 
     def _forward(self, z, scale, out):
         ops, pk, vae = self.ops, self.pk, self.vae
@@ -196,41 +172,17 @@ class VAEEncodeEngine(VAEDecodeEngine):
         assert x.dim() == 5
         self._check_weights(self.vae)
         key = ("enc", tuple(x.shape), x.dtype, x.device)
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = self._own(self._record_enc(x))
-            self._keep_plan(key, plan)
-        else:
-            plan["static"]["x"].copy_(x)
-            self._run(plan)
+        plan = self._lookup_or_record(key, lambda: self._record_enc(x), lambda st: st["x"].copy_(x))
         return plan["out"].clone()
 
     def _record_enc(self, x):
-        ops = self.ops
         self._begin(x.device)
         enc = self.vae.encoder
         b, c, t, H, W = x.shape
         down = 2 ** (enc.num_resolutions - 1)
         st = {"x": x.detach().clone().contiguous()}
         out = torch.empty(b, self.vae.quant_conv.weight.shape[0], t, H // down, W // down, dtype=torch.float32, device=x.device)
-        plan = {"static": st, "out": out, "runs": 0}
-
-        def body():
-            self._forward_enc(st["x"], out)
-
-        if getattr(ops, "is_native", False):
-            ops.init()
-            ops.recording = []
-            try:
-                body()
-            finally:
-                plan["rec"] = ops.recording
-                ops.recording = None
-        else:
-            plan["fn"] = body
-            body()
-        plan["pool_bytes"] = self.pool.bytes
-        return plan
+        return self._record_lists({"static": st, "out": out}, ("rec", lambda: self._forward_enc(st["x"], out)))
 
     def _forward_enc(self, x, out):
         ops, pk, vae = self.ops, self.pk, self.vae

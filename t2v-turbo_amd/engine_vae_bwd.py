@@ -22,23 +22,17 @@ from .vae import AttnBlock
 
 
 class VAEDecodeGradEngine(VAEDecodeEngine):
+    def __init__(self, vae, ops):
+        super().__init__(vae, ops)
+        self.use_graph = False   # T2V_HIP_GRAPH=1 does not apply here: hipGraph capture of this engine's two lists is not validated
+
     @on_tensor_device
     def decode_frames_tape(self, z, scale):
         """Forward like ``decode_frames`` but keeps what ``backward`` needs; returns the video (b, 3, t, 8h, 8w)."""
         assert z.dim() == 5
         self._check_weights(self.vae)
         key = ("grad", tuple(z.shape), z.dtype, float(scale), z.device)
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = self._own(self._record_grad(z, scale))
-            self._keep_plan(key, plan)
-            if getattr(self.ops, "is_native", False):
-                # recording executed the backward list once (on a zero gradient) and that recycled the saved forward
-                # buffers: run the forward list again so the tape holds this call's activations
-                self._replay(plan, "rec")
-        else:
-            plan["static"]["z"].copy_(z)
-            self._replay(plan, "rec")
+        plan = self._lookup_or_record(key, lambda: self._record_grad(z, scale), lambda st: st["z"].copy_(z))
         plan["fwd_id"] = plan.get("fwd_id", 0) + 1
         self._last = plan
         return plan["out"].clone()
@@ -47,23 +41,13 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
     def backward(self, dout):
         """d(loss)/dz for the most recent ``decode_frames_tape`` call."""
         plan = self._last
-        if plan.get("bwd_id") == plan["fwd_id"]:
-            raise RuntimeError("VAE decode gradient: backward was already run for this forward (its saved activations are gone)")
-        plan["bwd_id"] = plan["fwd_id"]
+        self._once_per_forward(plan, "VAE decode gradient")
         plan["static"]["dout"].copy_(dout)
         self._replay(plan, "rec_bwd")
         return plan["dz"].clone()
 
-    def _replay(self, plan, which):
-        ops = self.ops
-        if getattr(ops, "is_native", False):
-            ops.replay(plan[which], ops.stream())
-        else:
-            plan["fn" if which == "rec" else "fn_bwd"]()
-
     # ---- recording ----------------------------------------------------------------------------------------
     def _record_grad(self, z, scale):
-        ops = self.ops
         self._begin(z.device)
         dec = self.vae.decoder
         b, zc, t, h, w = z.shape
@@ -71,8 +55,7 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
         cout = leaf_out_channels(dec.conv_out)
         st = {"z": z.detach().clone().contiguous(),
               "dout": torch.zeros(b, cout, t, h * up, w * up, dtype=z.dtype, device=z.device)}
-        plan = {"static": st, "out": torch.empty_like(st["dout"]), "dz": torch.empty_like(st["z"]), "runs": 0}
-        native = getattr(ops, "is_native", False)
+        plan = {"static": st, "out": torch.empty_like(st["dout"]), "dz": torch.empty_like(st["z"])}
         self.tape = []
 
         def fwd():
@@ -82,25 +65,7 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
         def bwd():
             self._backward_tape(st["dout"], plan["dz"])
 
-        if native:
-            ops.init()
-            ops.recording = []
-            try:
-                fwd()
-            finally:
-                plan["rec"] = ops.recording
-                ops.recording = None
-            ops.recording = []
-            try:
-                bwd()
-            finally:
-                plan["rec_bwd"] = ops.recording
-                ops.recording = None
-        else:  # emulation backend (tests): the closures themselves are the plan; every forward is followed by one backward
-            fwd()
-            plan["fn"], plan["fn_bwd"] = fwd, bwd
-        plan["pool_bytes"] = self.pool.bytes
-        return plan
+        return self._record_lists(plan, ("rec", fwd), ("rec_bwd", bwd))
 
     # ---- helpers ------------------------------------------------------------------------------------------------
     def gn_t(self, x, norm, units, rows, silu):

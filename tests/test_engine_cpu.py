@@ -313,3 +313,104 @@ def test_width_320_transformer_linears_take_the_panel_resident_route():
         with torch.no_grad():
             y0 = eng(x, ts, ctx, 16, None, None)
         assert "linear_pr" not in ops.calls and rel_l2(y0, y) < 2e-5 and rel_l2(y0, y2) < 1e-6
+
+
+def test_inference_engines_under_the_record_replay_protocol():
+    """The UNet, VAE decode / encode and VAE decode gradient engines on the native backend's protocol (tests.emu_ops.ReplayOps:
+    launch lists recorded once, later calls refresh the static inputs and re-issue the lists) against the same engines
+    re-running their closures (EmuOps): the same launches on the same operands, so every output is bit-equal."""
+    from t2v_turbo_amd.engine_vae import VAEEncodeEngine
+    from t2v_turbo_amd.engine_vae_bwd import VAEDecodeGradEngine
+    from tests.emu_ops import ReplayOps
+    backends = (lambda: EmuOps(strict=True), ReplayOps)
+
+    def both(make, run, plan_of, lists, replays):
+        outs = []
+        for backend in backends:
+            ops = backend()
+            eng = make(ops)
+            with torch.no_grad():
+                outs.append(run(eng))
+            plan = plan_of(eng)
+            if ops.is_native:
+                assert all(k in plan for k in lists) and "fn" not in plan and "fn_bwd" not in plan
+                assert ops.replays == replays   # the later calls replayed the lists: nothing was recorded twice
+                assert len(eng.plans) == 1
+            else:
+                assert "fn" in plan and "rec" not in plan
+        assert len(outs[0]) == len(outs[1])
+        for a, b in zip(*outs):
+            assert torch.equal(a, b)
+        return plan
+
+    only_plan = lambda eng: next(iter(eng.plans.values()))  # noqa: E731
+    g = load("unet_tiny")
+    m = UNetModel(**tiny_unet_params()).eval()
+    m.load_state_dict(synth_state_dict(manifest("unet_tiny")), strict=True)
+    x2 = torch.randn(g["x"].shape, generator=torch.Generator().manual_seed(9))
+    plan = both(lambda ops: UNetEngine(m, ops),
+                lambda eng: [eng(g["x"], g["ts"], g["ctx"], 16, g["tc"], None), eng(x2, torch.tensor([519]), g["ctx"], 24, g["tc"], None)],
+                only_plan, ("rec",), 1)
+    assert len(plan["rec"]) > 500 and "rec_bwd" not in plan
+
+    gv = load("vae_tiny")
+    ae = AutoencoderKL(ddconfig=VAE_TINY_DD, embed_dim=4).eval()
+    ae.load_state_dict(synth_state_dict(manifest("vae_tiny")), strict=True)
+    z2 = torch.randn(gv["z"].shape, generator=torch.Generator().manual_seed(1))
+    scale = 1.0 / 0.18215
+    both(lambda ops: VAEDecodeEngine(ae, ops), lambda eng: [eng.decode_frames(gv["z"], scale), eng.decode_frames(z2, scale)],
+         only_plan, ("rec",), 1)
+
+    x5 = load("vae_tiny_enc")["x"].unsqueeze(0).transpose(1, 2).contiguous()
+    x6 = torch.randn(x5.shape, generator=torch.Generator().manual_seed(2))
+    both(lambda ops: VAEEncodeEngine(ae, ops), lambda eng: [eng.encode_frames(x5), eng.encode_frames(x6)], only_plan, ("rec",), 1)
+
+    def pairs(eng):
+        r = []
+        for z in (gv["z"], z2):
+            v = eng.decode_frames_tape(z, scale)
+            r += [v, eng.backward(torch.ones_like(v))]
+        return r
+
+    # recording runs both lists, then the forward list once more (the recorded backward recycled its saved buffers) and the
+    # backward list for the first pair; the second pair is one replay of each
+    both(lambda ops: VAEDecodeGradEngine(ae, ops), pairs, lambda eng: eng._last, ("rec", "rec_bwd"), 4)
+
+
+def test_launch_list_cut_at_host_calls():
+    """``engine.cut_at_host_calls``: the runs of launches that become one hipGraph each, and the host calls between them."""
+    from t2v_turbo_amd.engine import HOST_CALL, cut_at_host_calls
+
+    def launch(i):
+        return (print, (i,), f"t2v_launch_{i}")
+
+    def host(i):
+        return (len, (i,), HOST_CALL)
+
+    def check(rec):
+        runs = cut_at_host_calls(rec)
+        flat = []
+        for launches, call in runs:
+            assert (launches is None) != (call is None)
+            if call is None:
+                assert len(launches) > 0 and all(e[2] != HOST_CALL for e in launches)
+                flat += launches
+            else:
+                flat.append((call[0], call[1], HOST_CALL))
+        assert flat == rec   # the pieces, in order, are the list
+        for (a, _), (b, _) in zip(runs, runs[1:]):
+            assert a is None or b is None   # two runs of launches are never adjacent: only a host call ends a run
+        return runs
+
+    assert cut_at_host_calls([]) == []
+    plain = [launch(i) for i in range(5)]
+    runs = check(plain)
+    assert len(runs) == 1 and runs[0][0] is plain and runs[0][1] is None   # the list itself: its compiled program stays cached
+    L, H = launch, host
+    assert [r[0] is None for r in check([H(0), L(1), L(2)])] == [True, False]                      # first
+    assert [r[0] is None for r in check([L(0), L(1), H(2)])] == [False, True]                      # last
+    assert [r[0] is None for r in check([L(0), H(1), H(2), L(3)])] == [False, True, True, False]   # adjacent
+    assert [r[0] is None for r in check([H(0)])] == [True]                                         # alone
+    runs = check([H(0), L(1), H(2), L(3), L(4), H(5), H(6), L(7), H(8)])
+    assert [None if r[0] is None else len(r[0]) for r in runs] == [None, 1, None, 2, None, None, 1, None]
+    assert [r[1][1] for r in runs if r[0] is None] == [(0,), (2,), (5,), (6,), (8,)]
