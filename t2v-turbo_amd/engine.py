@@ -12,7 +12,6 @@ The engine is written against an *ops backend* (``native.HipOps``); tests substi
 emulation of the same interface to check the recorded dataflow on CPU.
 """
 import collections
-import math
 import os
 
 import torch
@@ -20,6 +19,7 @@ import torch.nn as nn
 
 from . import native as nt
 from .native import on_tensor_device
+from .packs import Packer, effective_weight_bias, is_lora_leaf, leaf_out_channels, params_fingerprint  # noqa: F401  (re-exported)
 from .unet3d import (Downsample, ResBlock, SpatialTransformer, TemporalTransformer, TimestepEmbedSequential,
                      Upsample)
 
@@ -93,300 +93,6 @@ class Act:
     @property
     def p1(self):
         return self.parts[1] if len(self.parts) > 1 else None
-
-
-# =================================================================================== weights
-def is_lora_leaf(mod):
-    """A LoraInjected{Linear,Conv2d,Conv3d} (utils/lora.py:19-230) by its children — dictionary lookups, not ``getattr``: a missing
-    attribute on an nn.Module costs an exception, and this runs over every module of the UNet on every training-path call."""
-    d = mod._modules
-    return "lora_up" in d and "lora_down" in d and (d.get("linear") is not None or d.get("conv") is not None)
-
-
-def effective_weight_bias(mod, merge=True):
-    """(weight, bias) of a Linear/Conv leaf; LoRA-injected leaves (utils/lora.py:19-230 layout:
-    .linear|.conv, .lora_down, .lora_up, .scale[, .selector]) are merged on the fly:
-    W + scale * up @ diag(sel) @ down — what ``collapse_lora`` (utils/lora.py:793-830) would bake in.
-    ``merge=False`` (the training engine, which runs the LoRA branch as its own GEMMs): the frozen base only."""
-    base = getattr(mod, "linear", None) or getattr(mod, "conv", None)
-    if base is not None and hasattr(mod, "lora_up") and hasattr(mod, "lora_down"):
-        if not merge:
-            return base.weight.detach(), base.bias
-        w = base.weight.detach().float()
-        up = mod.lora_up.weight.detach().float().flatten(1)
-        down = mod.lora_down.weight.detach().float().flatten(1)
-        sel = getattr(mod, "selector", None)
-        if isinstance(sel, (nn.Linear, nn.Conv2d, nn.Conv3d)):
-            up = up @ sel.weight.detach().float().flatten(1)
-        delta = (up @ down).reshape(w.shape)
-        return w + float(mod.scale) * delta, base.bias
-    return mod.weight.detach(), mod.bias
-
-
-def leaf_out_channels(mod):
-    """Output channels of a Linear / Conv leaf (a LoRA-injected leaf has its frozen base's) without merging anything."""
-    base = getattr(mod, "linear", None) or getattr(mod, "conv", None)
-    if base is not None and hasattr(mod, "lora_up") and hasattr(mod, "lora_down"):
-        return base.weight.shape[0]
-    return mod.weight.shape[0]
-
-
-class Packer:
-    """Packs leaf parameters into kernel layouts; cached until any parameter changes."""
-
-    def __init__(self, wdtype, device, merge_lora=True):
-        self.wdtype, self.device = wdtype, device
-        self.merge_lora = merge_lora
-        self.cache = {}
-        self.makers = {}
-
-    def wb(self, mod):
-        return effective_weight_bias(mod, self.merge_lora)
-
-    def _memo(self, key, fn):
-        if key not in self.cache:
-            self.cache[key] = fn()
-            self.makers[key] = fn
-        return self.cache[key]
-
-    def refresh(self, ops=None):
-        """Re-make every pack from the CURRENT parameters into the tensors that are already there (full fine-tuning: the weights move
-        every optimizer step, the recorded launch lists keep pointing at the same packs).  Entries are re-made in the order they were
-        first made, so a pack derived from another cached pack (transposes, fragment packs) sees its refreshed source.  ``ops``: the
-        op backend, for the packs the library re-makes itself (transposes of a refreshed pack, conv packs).
-        (Measured and not kept: the backward-only packs issued behind the forward's launches — 139.1 / 135.9 vs 139.8 / 135.2 ms per
-        step, profiles/r06_full_finetune_wgrad_affine_rework_ab.jsonl.)"""
-        def put(old, new):
-            if isinstance(old, torch.Tensor):
-                if old.data_ptr() != new.data_ptr():
-                    old.copy_(new)
-            elif isinstance(old, (tuple, list)):
-                for o, n in zip(old, new):
-                    put(o, n)
-        by_id = None
-        done = set()
-        for key, fn in list(self.makers.items()):
-            kind = key[0]
-            if kind == "full_idx":   # (index tables: no weights inside)
-                continue
-            alias = getattr(fn, "param", None)
-            if alias is not None and isinstance(self.cache[key], torch.Tensor) and alias.data_ptr() == self.cache[key].data_ptr():
-                continue                 # (an fp32 parameter on the device IS its pack: nothing to re-make)
-            if kind in ("mat", "mat_t") and len(key) == 2:
-                # the two most common packs straight from the parameter into the existing tensor: ONE cast-and-copy kernel instead of a
-                # cast into a temporary plus a device-to-device copy (1 100 of the 1 500 packs of the full-width UNet)
-                if by_id is None:
-                    by_id = getattr(self, "_mods_by_id", None)
-                mod = None if by_id is None else by_id.get(key[1])
-                src = self.cache.get(("mat", key[1])) if kind == "mat_t" and ("mat", key[1]) in done else None
-                if (src is not None and ops is not None and hasattr(ops, "transpose") and src.dtype == self.cache[key].dtype
-                        and (src.dtype == torch.bfloat16 or not src.is_cuda)):   # (the library's transpose is bf16; the emulated backend takes any)
-                    # the data-gradient pack = the forward pack transposed, bf16 -> bf16 by the library's tiled transpose (the strided
-                    # fp32 -> bf16 copy ran at ~ 300 GB/s: 30 us per pack, 7 ms per full fine-tuning step)
-                    ops.transpose(src, src.shape[0], src.shape[1], self.cache[key])
-                    done.add(key)
-                    continue
-                if mod is not None:
-                    w = self.wb(mod)[0].detach()
-                    w2 = w.reshape(w.shape[0], -1)
-                    self.cache[key].copy_(w2 if kind == "mat" else w2.t())
-                    done.add(key)
-                    continue
-            if getattr(fn, "into", False) and isinstance(self.cache[key], torch.Tensor):
-                fn(self.cache[key], ops)      # (a maker that writes straight into the existing pack)
-            else:
-                put(self.cache[key], fn())
-            done.add(key)
-
-    def f32(self, p):
-        if p is None:
-            return None
-        def make():
-            return p.detach().to(self.device, torch.float32).contiguous()
-        make.param = p       # (``refresh`` skips the pack while it still IS the parameter's storage)
-        return self._memo(("f32", id(p)), make)
-
-    def bias(self, mod):
-        b = self.wb(mod)[1]
-        if b is None:
-            return None
-        def make():
-            return b.detach().to(self.device, torch.float32).contiguous()
-        make.param = b
-        return self._memo(("bias", id(mod)), make)
-
-    def _remember(self, mod):
-        if not hasattr(self, "_mods_by_id"):
-            self._mods_by_id = {}
-        self._mods_by_id[id(mod)] = mod
-
-    def mat(self, mod):
-        """[N, K] row-major weight of a Linear / 1x1 conv / k=1 Conv1d."""
-        self._remember(mod)
-        def make():
-            w = self.wb(mod)[0]
-            return w.reshape(w.shape[0], -1).to(self.device, self.wdtype).contiguous()
-        return self._memo(("mat", id(mod)), make)
-
-    def conv(self, mod):
-        """[N, taps*Cin], tap-major: Conv2d [N,C,3,3] -> (ky,kx,c); Conv3d [N,C,3,1,1] -> (kt,c)."""
-        def make(out=None, ops=None):
-            return self._conv_tap_major(mod, out, ops)
-        make.into = True
-        return self._memo(("conv", id(mod)), make)
-
-    def _conv_tap_major(self, mod, out=None, ops=None):
-        w = self.wb(mod)[0]
-        if self._repacked(w, out, ops, 0):
-            return out
-        if w.dim() == 5:
-            w = w[:, :, :, 0, 0].permute(0, 2, 1)
-        else:
-            w = w.permute(0, 2, 3, 1)
-        return self._permuted_into(w, out)
-
-    @staticmethod
-    def _repacked(w, out, ops, kind):
-        """``refresh`` on the device: the conv parameter -> its existing bf16 pack by the library's repack kernel (t2v_repack_conv_f32;
-        kind 0 forward pack, 1 data-gradient pack).  False where that does not apply (first making, CPU tensors, a merged LoRA weight)."""
-        if out is None or ops is None or not hasattr(ops, "repack_conv") or w.dtype != torch.float32 or not w.is_contiguous():
-            return False
-        if os.environ.get("T2V_REPACK_NATIVE", "1") != "1":     # (A/B switch: torch's permute / flip / cast chain)
-            return False
-        if w.dim() == 5 and (w.shape[3] != 1 or w.shape[4] != 1):
-            return False
-        n, c = w.shape[0], w.shape[1]
-        taps = w.numel() // (n * c)
-        if taps > 9 or tuple(out.shape) != ((n, taps * c) if kind == 0 else (c, taps * n)) or not out.is_contiguous():
-            return False
-        if out.is_cuda and out.dtype != torch.bfloat16:
-            return False
-        ops.repack_conv(w, out, kind)
-        return True
-
-    def _permuted_into(self, w, out=None):
-        """The [rows, -1] pack of the permuted weight view ``w`` — into ``out`` where that is the existing pack (``refresh``: cast and
-        permutation as ONE kernel straight into the pack, no temporary and no second copy)."""
-        if out is not None and tuple(out.shape) == (w.shape[0], w[0].numel()) and out.is_contiguous():
-            out.view(w.shape).copy_(w)
-            return out
-        return w.reshape(w.shape[0], -1).to(self.device, self.wdtype).contiguous()
-
-    def conv_slab(self, mod):
-        """Slab-major pack of a 3x3 conv for t2v_conv_halo: [N][C/32][9][32], rows zero-padded to whole weight stages (native.pack_conv_slab)."""
-        def make():
-            cached = self.cache.get(("conv", id(mod)))   # (no second, tap-major copy is left behind for a conv the halo kernel takes)
-            return nt.pack_conv_slab(cached if cached is not None else self._conv_tap_major(mod))
-        return self._memo(("conv_slab", id(mod)), make)
-
-    def mat_t(self, mod):
-        """[K, N]^T pack of a Linear / 1x1 conv: the weight of its data gradient (dx = dy @ W)."""
-        self._remember(mod)
-        def make():
-            w = self.wb(mod)[0]
-            return w.reshape(w.shape[0], -1).t().to(self.device, self.wdtype).contiguous()
-        return self._memo(("mat_t", id(mod)), make)
-
-    def conv_dgrad(self, mod):
-        """3x3 conv data gradient as a 3x3 conv over dy: w'[ci][(ky',kx'), co] = w[co][ci][2-ky'][2-kx']."""
-        def make(out=None, ops=None):
-            w = self.wb(mod)[0]          # [co, ci, 3, 3]
-            if self._repacked(w, out, ops, 1):
-                return out
-            wd = w.flip(2, 3).permute(1, 2, 3, 0)      # [ci, ky', kx', co]
-            return self._permuted_into(wd, out)
-        make.into = True
-        return self._memo(("conv_dgrad", id(mod)), make)
-
-    def small_conv_dgrad(self, mod, cin_pad, cout_pad=None):
-        """fp32 [cout'][9][cin'] pack for the direct small-channel conv computing the data gradient of ``mod``:
-        cout' = mod's input channels (optionally zero-padded rows), cin' = mod's output channels padded to cin_pad."""
-        def make():
-            w = self.wb(mod)[0].float()  # [co, ci, 3, 3]
-            wd = w.flip(2, 3).permute(1, 2, 3, 0)      # [ci, ky', kx', co]
-            if cin_pad > wd.shape[-1]:
-                wd = torch.nn.functional.pad(wd, (0, cin_pad - wd.shape[-1]))
-            if cout_pad and cout_pad > wd.shape[0]:
-                wd = torch.nn.functional.pad(wd, (0, 0, 0, 0, 0, 0, 0, cout_pad - wd.shape[0]))
-            return wd.reshape(wd.shape[0], -1).to(self.device).contiguous()
-        return self._memo(("small_dgrad", id(mod), cin_pad, cout_pad), make)
-
-    def lpr(self, w):
-        """Fragment pack (native.pack_linear_pr) of an [N, K] pack this Packer made — a plain ``mat`` / ``cat_mats`` matrix or the 64-row
-        [value | gate] interleave of ``geglu`` — for t2v_linear_pr; keyed by the source pack, which the cache keeps alive."""
-        return self._memo(("lpr", id(w)), lambda: nt.pack_linear_pr(w))
-
-    def cat_mats(self, mods, tag):
-        return self._memo((tag,) + tuple(id(m) for m in mods),
-                          lambda: torch.cat([self.mat(m) for m in mods], dim=0).contiguous())
-
-    def geglu(self, proj):
-        """GEGLU projection packed in 64-row groups [32 value rows | 32 gate rows] (T2V_ACT_GEGLU)."""
-        def make():
-            w, b = self.wb(proj)
-            inner = w.shape[0] // 2
-            assert inner % 32 == 0
-            wv, wg = w[:inner].reshape(inner // 32, 32, -1), w[inner:].reshape(inner // 32, 32, -1)
-            wp = torch.cat([wv, wg], dim=1).reshape(2 * inner, -1).to(self.device, self.wdtype).contiguous()
-            bp = torch.cat([b[:inner].reshape(-1, 32), b[inner:].reshape(-1, 32)], dim=1).reshape(-1)
-            return wp, bp.detach().to(self.device, torch.float32).contiguous()
-        return self._memo(("geglu", id(proj)), make)
-
-    def mat_lnf(self, mods, norm, tag):
-        """LayerNorm folded into the Linear(s) that consume it (t2v_gemm lnf_*): (W' = cat(W) diag(gamma) in the weight dtype,
-        s = row sums of the ROUNDED W' (fp32: what the matrix cores multiply the mean with), t = b + cat(W) beta (fp32))."""
-        def make():
-            w = torch.cat([self.wb(m)[0].detach().float().reshape(self.wb(m)[0].shape[0], -1) for m in mods], dim=0).to(self.device)
-            b = torch.cat([(self.wb(m)[1].detach().float() if self.wb(m)[1] is not None else torch.zeros(self.wb(m)[0].shape[0]))
-                           .to(self.device) for m in mods])
-            gamma, beta = norm.weight.detach().float().to(self.device), norm.bias.detach().float().to(self.device)
-            wp = (w * gamma[None, :]).to(self.wdtype).contiguous()
-            return wp, wp.float().sum(dim=1).contiguous(), (b + w @ beta).contiguous()
-        return self._memo((tag, id(norm)) + tuple(id(m) for m in mods), make)
-
-    def geglu_lnf(self, proj, norm):
-        """``geglu`` pack (64-row groups [32 value | 32 gate]) of the LayerNorm-folded GEGLU projection: (W', s, t)."""
-        def make():
-            wp, s_vec, t_vec = self.mat_lnf([proj], norm, "geglu_lnf_src")
-            inner = wp.shape[0] // 2
-            assert inner % 32 == 0
-
-            def pack(v):
-                a, g = v[:inner].reshape(inner // 32, 32, -1), v[inner:].reshape(inner // 32, 32, -1)
-                return torch.cat([a, g], dim=1).reshape(2 * inner, -1)
-            return pack(wp).contiguous(), pack(s_vec[:, None]).reshape(-1).contiguous(), pack(t_vec[:, None]).reshape(-1).contiguous()
-        return self._memo(("geglu_lnf", id(proj), id(norm)), make)
-
-    def ffn(self, ff, norm):
-        """Packed operands of t2v_ffn_fused for FeedForward ``ff`` (GEGLU projection + output Linear) behind LayerNorm ``norm``."""
-        def make():
-            proj, lin = ff.net[0].proj, ff.net[2]
-            (w1, b1), (w2, b2) = self.wb(proj), self.wb(lin)
-            dev = self.device
-            return nt.ffn_pack(w1.detach().to(dev), None if b1 is None else b1.detach().to(dev), w2.detach().to(dev),
-                               None if b2 is None else b2.detach().to(dev), norm.weight.detach().to(dev), norm.bias.detach().to(dev),
-                               self.wdtype)
-        return self._memo(("ffn", id(ff), id(norm)), make)
-
-    def small_conv(self, mod, cin_pad=None):
-        """fp32 [cout][9][cin] for the direct small-Cin conv."""
-        def make():
-            w = self.wb(mod)[0].float().permute(0, 2, 3, 1)  # N,3,3,C
-            if cin_pad and cin_pad > w.shape[-1]:
-                w = torch.nn.functional.pad(w, (0, cin_pad - w.shape[-1]))
-            return w.reshape(w.shape[0], -1).to(self.device).contiguous()
-        return self._memo(("small", id(mod), cin_pad), make)
-
-
-def params_fingerprint(module, skip=()):
-    """Changes when any parameter is updated in place (version counter), re-homed (data pointer), added or removed."""
-    from .nn_util import walk_parameters
-    fp = 0
-    for p in walk_parameters(module):
-        if id(p) in skip:
-            continue
-        fp = (fp * 1000003 + p._version + (p.data_ptr() & 0xFFFFFFF)) & 0xFFFFFFFFFFFF
-    return fp
 
 
 # =================================================================================== base engine
@@ -661,9 +367,8 @@ class _Engine:
             return self.pk.conv_slab(mod)
         if w.dtype != self.adt:
             return None
-        # (``frozen_pack``: a caller-given pack of FROZEN weights — the data-gradient convs' flipped base weights, which live in the
-        # Packer's cache — is repacked once; packs that are rewritten every step, like the LoRA groups', must not be cached here)
-        return self.pk._memo(("conv_slab_of", id(w)), lambda: (w, nt.pack_conv_slab(w)))[1]
+        # (``frozen_pack``: the caller's pack is an entry of the Packer — the data-gradient convs' flipped base weights)
+        return self.pk.conv_slab_of(w)
 
     # where a LoRA conv leaf does better WITHOUT the epilogue form (profiles/r04_student_gemm_shapes.csv): (a) the plain launch would
     # split K (2560 x 1280 x 23040: 453 us in one split vs 162 us in four), (b) a 3x3 conv over >= ``lora_halo_min_c`` input channels
@@ -1012,8 +717,7 @@ class UNetEngine(_Engine):
         # every ResBlock's emb_layers Linear in one GEMM (rows are identical across frames: K17)
         lins = [rb.emb_layers[1] for rb in self._emb_table()[0]]
         w_all = pk.cat_mats(lins, "emb_all")
-        b_all = pk._memo(("emb_all_bias",) + tuple(id(l) for l in lins),
-                         lambda: torch.cat([pk.bias(l) for l in lins]).contiguous())
+        b_all = pk.cat_biases(lins, "emb_all_bias")
         self.emb_all = self.linear(emb_s, None, w=w_all, bias=b_all, out_dtype=torch.float32)
 
     def _context(self, st):

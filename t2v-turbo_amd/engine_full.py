@@ -115,24 +115,10 @@ class FullTrainMixin:
 
     # The refresh is ~ 2 000 small launches (torch copies / casts, library transposes and repacks) over FIXED tensors — the parameters'
     # storages in, the packs out — so after one eager pass it is captured as ONE hipGraph and replayed per optimizer step: the host's
-    # 15-17 ms of issuing it (tools/r6_gpu_calls/README.md, call 40) go.  The graph holds raw pointers: its signature names the Packer,
-    # every pack tensor and every parameter storage, and it is dropped and re-captured when a parameter was re-homed or a pack was added;
-    # T2V_REFRESH_GRAPH=0 keeps the eager loop.
+    # 15-17 ms of issuing it (profiles/r06_full_finetune_wgrad_affine_rework_ab.jsonl, refresh_graph 0 / 1) go.  The graph holds raw
+    # pointers: its signature names the Packer, every pack tensor and every parameter storage, and it is dropped and re-captured when a
+    # parameter was re-homed or a pack was added; T2V_REFRESH_GRAPH=0 keeps the eager loop.
     refresh_graph = os.environ.get("T2V_REFRESH_GRAPH", "1") == "1"
-
-    @staticmethod
-    def _pack_ptrs(pk):
-        ptrs = []
-
-        def walk(v):
-            if isinstance(v, torch.Tensor):
-                ptrs.append(v.data_ptr())
-            elif isinstance(v, (tuple, list)):
-                for e in v:
-                    walk(e)
-        for v in pk.cache.values():
-            walk(v)
-        return tuple(ptrs)
 
     def _refresh(self, plan):
         pk = plan["owned"][1]
@@ -142,7 +128,7 @@ class FullTrainMixin:
             pk.refresh(self.ops)
             return
         from .nn_util import walk_parameters
-        sig = (id(pk), self._pack_ptrs(pk), tuple(p.data_ptr() for p in walk_parameters(self.model)))
+        sig = (id(pk), pk.pointers(), tuple(p.data_ptr() for p in walk_parameters(self.model)))
         st = plan.get("refresh")
         if st is not None and st["sig"] == sig and st["graph"] is not None:
             st["graph"].replay()
@@ -220,7 +206,7 @@ class FullTrainMixin:
         return g
 
     def _idx(self, key, make):
-        return self.pk._memo(("full_idx",) + key, lambda: make().to(torch.int32).to(self.device).contiguous())
+        return self.pk.pack(("full_idx",) + key, lambda: make().to(torch.int32).to(self.device).contiguous(), static=True)
 
     def full_wgrad(self, dy, xmat, out):
         """out[R, C] = dy^T xmat by t2v_wgrad_tn (one launch pair, or one launch where the product has enough output tiles to fill the

@@ -210,7 +210,7 @@ class LoraTrainMixin:
             for tap in range(taps):
                 w[tap, :, taps - 1 - tap, :] = torch.eye(rp)
             return w.reshape(taps * rp, taps * rp).to(self.device, self.adt).contiguous()
-        return self.pk._memo(("lora_sel", taps, rp), make)
+        return self.pk.pack(("lora_sel", taps, rp), make, static=True)
 
     def clip_indicator(self, m_rows):
         """[B, Mp] bf16, 1 on the rows of clip b: A operand of the column-sum GEMM (d loss / d emb_all)."""
@@ -222,7 +222,7 @@ class LoraTrainMixin:
             for b in range(B):
                 ind[b, b * per:(b + 1) * per] = 1
             return ind.to(self.device, self.adt).contiguous()
-        return self.pk._memo(("clip_ind", m_rows, self.B), make)
+        return self.pk.pack(("clip_ind", m_rows, self.B), make, static=True)
 
     def clip_indicator_tok(self, m_rows):
         """[M, 8] bf16, column b = 1 on the rows of clip b: the token-major operand of the column sums for t2v_wgrad_tn."""
@@ -234,7 +234,7 @@ class LoraTrainMixin:
             for b in range(B):
                 ind[b * per:(b + 1) * per, b] = 1
             return ind.to(self.device, self.adt).contiguous()
-        return self.pk._memo(("clip_ind_tok", m_rows, self.B), make)
+        return self.pk.pack(("clip_ind_tok", m_rows, self.B), make, static=True)
 
     # ---- groups -------------------------------------------------------------------------------------------------------
     def lgroup(self, mods, mode, perm=None):

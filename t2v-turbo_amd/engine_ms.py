@@ -36,8 +36,7 @@ class MSUNetEngine(UNetEngine):
         ops.silu(emb, emb_s)
         lins = [rb.time_emb_proj for rb in self._emb_table(ResnetBlock2D)[0]]
         w_all = pk.cat_mats(lins, "ms_emb_all")
-        b_all = pk._memo(("ms_emb_all_bias",) + tuple(id(l) for l in lins),
-                         lambda: torch.cat([pk.bias(l) for l in lins]).contiguous())
+        b_all = pk.cat_biases(lins, "ms_emb_all_bias")
         self.emb_all = self.linear(emb_s, None, w=w_all, bias=b_all, out_dtype=torch.float32)
         # ---- text context, shared by all frames of a clip
         self._context(st)

@@ -306,22 +306,6 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         self.pool.put(ws)
         return dx
 
-    def tconv_dgrad_w(self, mod):
-        """(3,1,1) conv data gradient as the same temporal conv over dy: w'[ci][(kt', co)] = w[co][ci][2 - kt']."""
-        def make(out=None, ops=None):
-            w = self.pk.wb(mod)[0]                                  # [co, ci, 3, 1, 1]
-            if self.pk._repacked(w, out, ops, 1):
-                return out
-            wd = w[:, :, :, 0, 0].flip(2).permute(1, 2, 0)          # [ci, kt', co]
-            return self.pk._permuted_into(wd, out)
-        make.into = True
-        return self.pk._memo(("tconv_dgrad", id(mod)), make)
-
-    def mats_t(self, mods, tag):
-        """Transposed pack of row-concatenated Linear weights: [K, sum N] (dx = d[y0|y1|..] @ cat(W))."""
-        return self.pk._memo((tag,) + tuple(id(mm) for mm in mods),
-                             lambda: self.pk.cat_mats(mods, tag + "_fwd").t().contiguous())
-
     def drop_site(self, drops, kind, meta=None):
         """(p, site id) of an active dropout (None if inactive).  ``drops``: the nn.Dropout module(s) this site stands for
         (one per leaf of a LoRA group); kind / meta describe the row order for tests that replay the masks in torch."""
@@ -435,7 +419,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         ops = self.ops
         n, h, w = in_geom
         m_in = n * h * w
-        base = self.tconv_dgrad_w(mod) if mode == nt.GEMM_TCONV3 else self.pk.conv_dgrad(mod)
+        base = self.pk.tconv_dgrad(mod) if mode == nt.GEMM_TCONV3 else self.pk.conv_dgrad(mod)
         inner_mode = nt.GEMM_TCONV3 if mode == nt.GEMM_TCONV3 else nt.GEMM_CONV3X3
 
         def run(src, wpack, residual=None, odt=None, pool=True, frozen=False):
@@ -942,7 +926,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                 ops.attn_temporal_bwd(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], d_o, dprobs,
                                       dqkv[:, :inner], dqkv[:, inner:2 * inner], dqkv[:, 2 * inner:], B, F, hw, attn.heads, attn.scale)
                 self.pool.put(qkv, d_o)
-                d_ln = self.lin_b(dqkv, self.mats_t(mods, "qkv_t"), lora=mods)
+                d_ln = self.lin_b(dqkv, self.pk.mats_t(mods, "qkv_t"), lora=mods)
                 self.pool.put(dqkv)
                 return d_ln
             return o, bwd
@@ -992,7 +976,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                                      n_img, hw, heads, attn.scale)
                 self.pool.put(kT, qT, doT, l2, dsum, v_buf, vt, qk, d_o)
                 self.drop(o)
-                d1 = self.lin_b(dqk, self.mats_t([attn.to_q, attn.to_k], "qk_t"), lora=[attn.to_q, attn.to_k])
+                d1 = self.lin_b(dqk, self.pk.mats_t([attn.to_q, attn.to_k], "qk_t"), lora=[attn.to_q, attn.to_k])
                 d_ln = self.lin_b(d_v, pk.mat_t(attn.to_v), residual=d1, lora=[attn.to_v])
                 self.pool.put(dqk, d_v, d1)
                 return d_ln
@@ -1044,7 +1028,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                 ops.gemm(dsT, qT, dqk[:, inner:inner + 64], M=hw, N=64, alpha=attn.scale, a_strides=(heads * kp * kp, kp * kp),
                          w_strides=(inner * kp, 64 * kp), o_strides=(hw * 2 * inner, 64), **hb)
                 self.pool.put(dsT, qT)
-                d1 = self.lin_b(dqk, self.mats_t([attn.to_q, attn.to_k], "qk_t"), lora=[attn.to_q, attn.to_k])
+                d1 = self.lin_b(dqk, self.pk.mats_t([attn.to_q, attn.to_k], "qk_t"), lora=[attn.to_q, attn.to_k])
                 d_ln = self.lin_b(d_v, pk.mat_t(attn.to_v), residual=d1, lora=[attn.to_v])
                 self.pool.put(dqk, d_v, d1)
                 return d_ln
@@ -1155,7 +1139,7 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             d_h = self.buf(M, hpre.shape[1])
             ops.geglu_bwd(hpre, d_g, d_h)
             self.pool.put(d_g, hpre)
-            d_ln3 = self.lin_b(d_h, pk._memo(("geglu_t", id(proj.proj)), lambda: wg.t().contiguous()), lora=[proj.proj])
+            d_ln3 = self.lin_b(d_h, pk.geglu_t(proj.proj), lora=[proj.proj])
             self.pool.put(d_h)
             d_y2 = ln_b(blk.norm3, y2, d_ln3, dy3)
             self.pool.put(d_ln3, dy3, y2)

@@ -76,7 +76,7 @@ class VAEDecodeEngine(_Engine):
             b8[: wq.shape[0]] = pq.bias.detach().float().cpu()
             return w3.reshape(8, -1).to(self.device).contiguous(), b8.to(self.device)
 
-        w3, b8 = pk._memo(("pq", id(pq), float(scale)), pq_weights)
+        w3, b8 = pk.pack(("pq", id(pq), float(scale)), pq_weights)
         z8 = self.buf(n_img * h * w, 8)
         ops.conv_small(zt, n_img, h, w, w3, b8, z8)
         cin_w = pk.small_conv(dec.conv_in, cin_pad=8)
@@ -227,7 +227,7 @@ class VAEEncodeEngine(VAEDecodeEngine):
             bf = (wq @ enc.conv_out.bias.detach().float() + vae.quant_conv.bias.detach().float()).to(self.device).contiguous()
             return wf, bf
 
-        wf, bf = pk._memo(("enc_out", id(enc.conv_out), id(vae.quant_conv)), folded)
+        wf, bf = pk.pack(("enc_out", id(enc.conv_out), id(vae.quant_conv)), folded)
         mom = self.buf(n_img * a.h * a.w, wf.shape[0], torch.float32)
         ops.gemm(tt, wf, mom, M=n_img * a.h * a.w, N=wf.shape[0], mode=nt.GEMM_CONV3X3, n_img=n_img, h=a.h, wd=a.w, bias=bf)
         self.pool.put(tt)

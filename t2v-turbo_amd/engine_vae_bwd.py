@@ -114,7 +114,7 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
             w3[:zc, 4, : wq.shape[0]] = wq.t().cpu()
             return w3.reshape(8, -1).to(self.device).contiguous()
 
-        w3, b8 = pk._memo(("pq", id(pq), float(scale)), pq_weights)
+        w3, b8 = pk.pack(("pq", id(pq), float(scale)), pq_weights)
         z8 = self.buf(n_img * h * w, 8)
         ops.conv_small(zt, n_img, h, w, w3, b8, z8)
         h0 = self.buf(n_img * h * w, leaf_out_channels(dec.conv_in))
@@ -123,11 +123,12 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
 
         def entry_bwd(dy, dz_out):
             # conv_in data gradient (512 -> the 4 real post-quant channels), then post_quant_conv^T, then back to NCFHW
-            wd = pk._memo(("conv_in_dgrad", id(dec.conv_in)), lambda: pk.conv_dgrad(dec.conv_in)[:4].contiguous())
+            wd = pk.pack(("conv_in_dgrad", id(dec.conv_in)), lambda: pk.conv_dgrad(dec.conv_in)[:4].contiguous(),
+                         src=[("conv_dgrad", id(dec.conv_in))])
             d4 = self.conv(dy, dec.conv_in, nt.GEMM_CONV3X3, w=wd, bias=None)
             self.pool.put(dy.t)
             d8 = self.buf(n_img * h * w, 8)
-            ops.conv_small(d4.t, n_img, h, w, pk._memo(("pq_dgrad", id(pq), float(scale)), pq_dgrad_weights), None, d8)
+            ops.conv_small(d4.t, n_img, h, w, pk.pack(("pq_dgrad", id(pq), float(scale)), pq_dgrad_weights), None, d8)
             self.pool.put(d4.t)
             ops.tokens_to_ncfhw(d8, dz_out)
             self.pool.put(d8)

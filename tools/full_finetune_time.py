@@ -71,11 +71,11 @@ def main():
         for _ in range(3):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            eng._refresh() if hasattr(eng, "_refresh") else eng.pk.refresh(eng.ops)
+            eng._refresh(eng._last)
             t1 = time.perf_counter()
             torch.cuda.synchronize()
             best = min(best, ((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
-        out["pack_refresh_ms"] = {"host_issue": round(best[0], 2), "until_device_done": round(best[1], 2), "packs": len(eng.pk.makers)}
+        out["pack_refresh_ms"] = {"host_issue": round(best[0], 2), "until_device_done": round(best[1], 2), "packs": len(eng.pk)}
     out.update(path="native gradient engine" if args.native else "torch composite (ATen kernels)", record_ms=round(times[0], 1),
                step_ms=[round(t, 1) for t in times[1:]], loss=float(loss.detach()), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1))
     if args.native:
