@@ -602,6 +602,58 @@ int t2v_norm_affine_grad(const void* x0, int c0, int ld0, const void* x1, int c1
  * torch's permute / flip / cast chain for the conv leaves (70 % of the UNet's parameters).  Pure data movement: every element is the
  * round-to-nearest-even bf16 of one parameter; ldo below the pack row is refused, columns behind the pack row are not written. */
 int t2v_repack_conv_f32(const float* w, int N, int C, int taps, int kind, void* out, int ldo, void* stream);
+/* ---- the B-row conditioning branch of the training routes (csrc/full_grad.hip) -----------------------------------------------------
+ * The time / fps / guidance MLPs (time_embed, fps_embedding, time_cond_proj, motion_cond_proj, combine_proj: openaimodel3d.py:683-706) and
+ * the SiLU -> Linear emb_layers of every ResBlock (openaimodel3d.py:172-178) have M = B rows, B = clips of the batch.  Three entries run
+ * their forward, data gradient and weight gradient — and, composed, the LoRA branch of an injected leaf (down -> up -> mask * scale -> add:
+ * utils/lora.py:45-50) — in fp32 on the master parameters IN PLACE: no packs, nothing to refresh after an optimizer step.  They replace the
+ * F.linear / F.silu calls of those lines and their autograd nodes.
+ * Shared conventions: 1 <= B <= T2V_ROWLIN_MAX_ROWS rows; activations and gradients fp32 [B][ld]; weights [N][ldw] fp32, or bf16 with
+ * w_bf16 != 0, read with 16-byte loads where the base is 16-byte aligned and ldw a multiple of 16 bytes (element loads otherwise — same
+ * sums in the same order); a TABLE of n problems per call, all of them in one launch (pair); tables of any length are taken (split into
+ * launches of 24 problems inside the library).  Only rows [0, B) and columns [0, K) / [0, N) of any operand are read or written: padding
+ * columns behind a row and rows past B are never touched.  fp32 accumulation in a fixed order, no float atomics: two calls with the same
+ * arguments give the same bits.  SiLU and its derivative are evaluated in double and rounded once.  Refused before anything is launched:
+ * a null table or operand and B outside 1..8 (T2V_EINVAL), a row stride shorter than the row (T2V_ESHAPE). */
+#define T2V_ROWLIN_MAX_ROWS 8
+typedef struct t2v_rowlin_problem {
+    const float* x;     /* fwd, wgrad: the leaf's input [B][ldx], columns [0, K).  bwd_data: the saved pre-activation of dx (silu != 0), else unused */
+    const void* w;      /* fwd, bwd_data: weights [N][ldw], columns [0, K); fp32, or bf16 if w_bf16.  wgrad: unused */
+    const float* bias;  /* fwd: [N] or NULL */
+    const float* res;   /* fwd: residual [B][ldr], columns [0, N), or NULL */
+    float* y;           /* fwd: the output [B][ldy], columns [0, N) (written).  bwd_data, wgrad: dy, the gradient of that output (read) */
+    float* dx;          /* bwd_data: the input gradient [B][ldo], columns [0, K) (written, or added to if accumulate) */
+    float* dw;          /* wgrad: the weight gradient [N][ldo], columns [0, K), fp32 (written, or added to if accumulate) */
+    float* db;          /* wgrad: the bias gradient [N] (as dw), or NULL */
+    int K, N;           /* input / output features */
+    int ldx, ldw, ldy, ldr, ldo;
+    int w_bf16;         /* weights are bf16 (the reference sums use the bf16 values as they are) */
+    int silu;           /* fwd, wgrad: f = SiLU on the input x (else identity).  bwd_data: g = silu'(x) on the result (else 1) */
+    int accumulate;     /* bwd_data, wgrad: += into dx / dw / db */
+    float alpha;        /* scale of the problem's sum: fwd y = bias + alpha sum (+ res); bwd_data: alpha_p on problem p's sum; wgrad: dw (db is not scaled) */
+    int reserved;
+} t2v_rowlin_problem;
+/* t2v_rowlin_fwd, per problem:  y[b][n] = bias[n] + alpha sum_k f(x[b][k]) w[n][k] (+ res[b][n]).  One pass over w: a wave owns four rows, a lane the
+ * 16-byte chunks l, l + 64, ... of each with B accumulators per row, then a butterfly.  f(x) of a problem waits in LDS: B * K <= 16384
+ * (T2V_ESHAPE beyond).  y must not overlap x or res of the same table. */
+int t2v_rowlin_fwd(const t2v_rowlin_problem* problems, int n, int B, void* stream);
+/* t2v_rowlin_bwd_data:  dx[b][k] (+)= g(x[b][k]) * sum_p alpha_p sum_n dy_p[b][n] w_p[n][k], the outer sum over ALL problems of the table that name
+ * the same dx (the 22 emb_layers behind one d(silu(emb)); a LoRA leaf's base weight and its down-projection): they must agree on K, ldo,
+ * silu, accumulate (and x, ldx if silu), T2V_EINVAL otherwise.  The contraction runs over the weight's row index, so N is split over
+ * workgroups in runs of 64 rows: partial sums [split][B][K] go to ws (t2v_rowlin_ws_floats(problems, n, B) floats, fp32; ws_floats is
+ * checked) and a second launch adds them per dx — problems in table order, their splits in order — applies g and writes.  Only the first
+ * t2v_rowlin_ws_floats floats of ws are written. */
+long long t2v_rowlin_ws_floats(const t2v_rowlin_problem* problems, int n, int B);
+int t2v_rowlin_bwd_data(const t2v_rowlin_problem* problems, int n, int B, float* ws, long long ws_floats, void* stream);
+/* t2v_rowlin_wgrad:  dw[n][k] (+)= alpha sum_b dy[b][n] f(x[b][k]),  db[n] (+)= sum_b dy[b][n]  (b in order 0 .. B - 1), fp32, straight into the
+ * gradient tensor the caller names (row stride ldo >= K; 16-byte stores where dw is 16-byte aligned and ldo % 4 == 0): a streaming write. */
+int t2v_rowlin_wgrad(const t2v_rowlin_problem* problems, int n, int B, void* stream);
+/* t2v_dropout_bf16 (below) on fp32 rows, same mask bit for bit: out[r][c] = keep(r, c) ? x[r][c] / (1 - p') : 0 (+ resid[r][c]) — the dropout of
+ * the conditioning leaves' B-row LoRA branches (utils/lora.py:45-50).  ncols even, strides >= ncols (checked); in place allowed. */
+int t2v_dropout_f32(const float* x, int ldx, const float* resid, int ldr, float* out, int ldo, long long rows, int ncols, float p,
+                    const void* seed, unsigned site, void* stream);
+/* t2v_timestep_embedding with an fp32 result [n][dim] (contiguous): the input of the fp32 conditioning branch above. */
+int t2v_timestep_embedding_f32(const void* t, int t_is_f32, int n, int dim, int guidance_style, float* out, void* stream);
 /* t2v_transpose_pad_bf16: out[b][c][r] = in[b][r][c] for r < rows and 0 for rows <= r < roundup(rows, 64) — the K-contiguous,
  * K-padded operand of the token-contracted weight-gradient GEMMs (dU = dy^T t, dD = G^T x) in one pass; 16-byte accesses on both
  * sides: cols % 8 == 0, ld_in % 8 == 0, ld_out % 8 == 0 and >= roundup(rows, 64), 16-byte aligned bases, batch strides % 8. */

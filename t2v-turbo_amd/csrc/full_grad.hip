@@ -19,7 +19,14 @@
 //    (engine.Packer.refresh): a conv leaf's fp32 parameter [N][C][taps] into its tap-major forward pack [N][taps][C] or its data-gradient
 //    pack [C][taps flipped][N], cast included, through an LDS tile so that both sides are coalesced (torch's strided cast-and-copy did
 //    37 us per pack, ~ 300 GB/s: profiles/r06_full_finetune_kernel_stats.csv).
+//  * t2v_rowlin_fwd / t2v_rowlin_bwd_data / t2v_rowlin_wgrad — the B-row conditioning branch of the training routes (time / fps / guidance
+//    MLPs and every ResBlock's SiLU -> Linear emb_layers: openaimodel3d.py:683-706,172-178; their LoRA branches: utils/lora.py:45-50), B <= 8
+//    rows, on the fp32 master parameters IN PLACE: no packs, no refresh, fp32 arithmetic end to end.  Every kernel reads or writes each
+//    weight-sized array once with 16-byte accesses (HBM-bound: the 22 emb_layers weights are ~ 103 MB at full width); a table of problems
+//    per launch (all emb_layers in one), fixed summation order, no float atomics.  The row counts per workgroup below are first choices,
+//    not tuned ones: nothing here has been timed against an alternative.
 #include "common.h"
+#include <math.h>
 
 namespace {
 
@@ -265,6 +272,310 @@ __global__ __launch_bounds__(256) void repack_conv_dgrad_kernel(const float* __r
     }
 }
 
+// ---- B-row linear family -----------------------------------------------------------------------------------------------------------------
+constexpr int RL_MAXP = 24;         // problems per launch: the table is a kernel argument (24 x 112 bytes + the offsets below < 4 KB)
+constexpr int RL_FWD_ROWS = 32;     // weight rows per forward workgroup (4 waves x 2 passes x 4 rows)
+constexpr int RL_SPLIT_ROWS = 64;   // weight rows per workgroup of bwd_data (one N split) and wgrad
+constexpr int RL_LDS_FLOATS = 16384;   // f(x) of one forward problem in LDS: B * K floats, 64 KB
+
+struct RowlinTable {
+    t2v_rowlin_problem p[RL_MAXP];
+    long long ws_off[RL_MAXP];      // bwd_data: first float of the problem's partial sums [nsplit][B][K]
+    int first[RL_MAXP + 1];         // block prefix sums
+    int nsplit[RL_MAXP];            // bwd_data: N splits of RL_SPLIT_ROWS rows
+    int lead[RL_MAXP];              // bwd_data: per distinct dx, the first problem that names it
+    int n, B, ngroups;
+};
+
+// SiLU and its derivative in double, rounded once: the fp32 error budget of these entries is a few roundings per output (B = 1, N = 1)
+__device__ __forceinline__ float rl_silu(float v) { return (float)((double)v / (1.0 + exp(-(double)v))); }
+__device__ __forceinline__ float rl_dsilu(float v) {
+    const double sg = 1.0 / (1.0 + exp(-(double)v));
+    return (float)(sg * (1.0 + (double)v * (1.0 - sg)));
+}
+
+// elements [k0, k0 + VEC) of one weight row as floats (VEC = 4 fp32 / 8 bf16: 16 bytes); at or past K: 0, never read
+template <int WB>
+__device__ __forceinline__ void rl_load_w(const void* w, long long row_off, int k0, int K, bool vec, float* f) {
+    if (WB) {
+        const bf16_t* r = (const bf16_t*)w + row_off;
+        if (vec && k0 + 8 <= K) { const uint4 v = *(const uint4*)(r + k0); unpack8(v, f); }
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = k0 + e < K ? bf2f(r[k0 + e]) : 0.f;
+        }
+    } else {
+        const float* r = (const float*)w + row_off;
+        if (vec && k0 + 4 <= K) { const float4 v = *(const float4*)(r + k0); f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[e] = k0 + e < K ? r[k0 + e] : 0.f;
+        }
+    }
+}
+
+// y[b][n] = bias[n] + sum_k xs[b][k] W[n][k] (+ res[b][n]).  A wave owns four weight rows at a time: lane l holds the 16-byte chunks l, l + 64, ...
+// of each (one pass over W), B accumulators per row, then one butterfly per (row, b).
+template <int WB>
+__device__ __forceinline__ void rl_fwd_body(const t2v_rowlin_problem& p, int B, int n_blk0, const float* xs) {
+    constexpr int VEC = WB ? 8 : 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = p.K, N = p.N, nch = (K + VEC - 1) / VEC;
+    const bool wvec = (uintptr_t)p.w % 16 == 0 && p.ldw % VEC == 0;
+    for (int pass = 0; pass < RL_FWD_ROWS / 16; ++pass) {
+        const int n0 = n_blk0 + pass * 16 + wave * 4;
+        if (n0 >= N) break;   // (wave-uniform)
+        float acc[4][T2V_ROWLIN_MAX_ROWS];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) acc[r][b] = 0.f;
+        for (int c = lane; c < nch; c += 64) {
+            const int k0 = c * VEC;
+            float wv[4][VEC];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (n0 + r < N) rl_load_w<WB>(p.w, (long long)(n0 + r) * p.ldw, k0, K, wvec, wv[r]);
+                else {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) wv[r][e] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+                if (b < B) {
+                    float xv[VEC];
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) xv[e] = k0 + e < K ? xs[b * K + k0 + e] : 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) acc[r][b] += xv[e] * wv[r][e];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+                if (b < B) {
+                    float v = wave_sum(acc[r][b]) * p.alpha;
+                    const int n = n0 + r;
+                    if (lane == r * T2V_ROWLIN_MAX_ROWS + b && n < N) {
+                        if (p.bias) v += p.bias[n];
+                        if (p.res) v += p.res[(long long)b * p.ldr + n];
+                        p.y[(long long)b * p.ldy + n] = v;
+                    }
+                }
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void rowlin_fwd_kernel(const RowlinTable t) {
+    extern __shared__ float rl_xs[];   // f(x) [B][K] of this block's problem
+    int i = 0;
+    while (i + 1 < t.n && (int)blockIdx.x >= t.first[i + 1]) ++i;   // block-uniform
+    const t2v_rowlin_problem& p = t.p[i];
+    const int B = t.B, K = p.K;
+    for (int j = threadIdx.x; j < B * K; j += 256) {
+        const int b = j / K, k = j - b * K;
+        const float v = p.x[(long long)b * p.ldx + k];
+        rl_xs[j] = p.silu ? rl_silu(v) : v;
+    }
+    __syncthreads();
+    const int n_blk0 = ((int)blockIdx.x - t.first[i]) * RL_FWD_ROWS;
+    if (p.w_bf16) rl_fwd_body<1>(p, B, n_blk0, rl_xs);
+    else rl_fwd_body<0>(p, B, n_blk0, rl_xs);
+}
+
+// Stage 1 of bwd_data: block (problem, N split, tile of 64 column chunks), one wave.  Lane l owns the 16-byte column chunk 64 tile + l of every
+// weight row of the split (rows in order: a fixed sum), dy of the split's rows waits in LDS; partial[b][k] goes to the workspace.
+template <int WB>
+__device__ __forceinline__ void rl_bwd_body(const t2v_rowlin_problem& p, int B, int n0, int rows, int kt, float* part, const float (*sdy)[RL_SPLIT_ROWS]) {
+    constexpr int VEC = WB ? 8 : 4;
+    const int K = p.K, k0 = (kt * 64 + (int)threadIdx.x) * VEC;
+    if (k0 >= K) return;
+    const bool wvec = (uintptr_t)p.w % 16 == 0 && p.ldw % VEC == 0;
+    float acc[T2V_ROWLIN_MAX_ROWS][VEC];
+#pragma unroll
+    for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[b][e] = 0.f;
+#pragma unroll 4
+    for (int r = 0; r < rows; ++r) {
+        float wv[VEC];
+        rl_load_w<WB>(p.w, (long long)(n0 + r) * p.ldw, k0, K, wvec, wv);
+#pragma unroll
+        for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+            if (b < B) {
+                const float d = sdy[b][r];
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[b][e] += d * wv[e];
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+        if (b < B) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (k0 + e < K) part[(long long)b * K + k0 + e] = acc[b][e] * p.alpha;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void rowlin_bwd_partial_kernel(const RowlinTable t, float* __restrict__ ws) {
+    __shared__ float sdy[T2V_ROWLIN_MAX_ROWS][RL_SPLIT_ROWS];
+    int i = 0;
+    while (i + 1 < t.n && (int)blockIdx.x >= t.first[i + 1]) ++i;
+    const t2v_rowlin_problem& p = t.p[i];
+    const int B = t.B, VEC = p.w_bf16 ? 8 : 4;
+    const int ktiles = ((p.K + VEC - 1) / VEC + 63) / 64;
+    const int local = (int)blockIdx.x - t.first[i], split = local / ktiles, kt = local - split * ktiles;
+    const int n0 = split * RL_SPLIT_ROWS, rows = min(RL_SPLIT_ROWS, p.N - n0);
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b)
+        if (b < B) sdy[b][lane] = lane < rows ? p.y[(long long)b * p.ldy + n0 + lane] : 0.f;
+    __syncthreads();
+    float* part = ws + t.ws_off[i] + (long long)split * B * p.K;
+    if (p.w_bf16) rl_bwd_body<1>(p, B, n0, rows, kt, part, sdy);
+    else rl_bwd_body<0>(p, B, n0, rows, kt, part, sdy);
+}
+
+// Stage 2: dx[b][k] (+)= g(pre[b][k]) * (sum of the partial sums of every problem that names this dx: problems in table order, their splits in
+// order).  Block (256 values of [B][K], distinct dx).
+__global__ __launch_bounds__(256) void rowlin_bwd_finish_kernel(const RowlinTable t, const float* __restrict__ ws) {
+    const t2v_rowlin_problem& q = t.p[t.lead[blockIdx.y]];
+    const int B = t.B, K = q.K;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= B * K) return;
+    const int b = idx / K, k = idx - b * K;
+    const long long slab = (long long)B * K;
+    float s = 0.f;
+    for (int i = 0; i < t.n; ++i) {
+        if (t.p[i].dx != q.dx) continue;
+        const float* src = ws + t.ws_off[i] + idx;
+        const int ns = t.nsplit[i];
+#pragma unroll 4
+        for (int sp = 0; sp < ns; ++sp) s += src[sp * slab];
+    }
+    if (q.silu) s *= rl_dsilu(q.x[(long long)b * q.ldx + k]);
+    float* d = q.dx + (long long)b * q.ldo + k;
+    *d = q.accumulate ? *d + s : s;
+}
+
+// dW[n][k] (+)= alpha sum_b dy[b][n] f(x[b][k]), db[n] (+)= sum_b dy[b][n]: block (problem, RL_SPLIT_ROWS weight rows, tile of 64 four-column
+// chunks), one wave.  Lane l keeps f(x[:, chunk]) in registers and streams its 16 bytes of every row out; the first column tile also writes db.
+__global__ __launch_bounds__(64) void rowlin_wgrad_kernel(const RowlinTable t) {
+    __shared__ float sdy[T2V_ROWLIN_MAX_ROWS][RL_SPLIT_ROWS];
+    int i = 0;
+    while (i + 1 < t.n && (int)blockIdx.x >= t.first[i + 1]) ++i;
+    const t2v_rowlin_problem& p = t.p[i];
+    const int B = t.B, K = p.K;
+    const int ktiles = ((K + 3) / 4 + 63) / 64;
+    const int local = (int)blockIdx.x - t.first[i], rblk = local / ktiles, kt = local - rblk * ktiles;
+    const int n0 = rblk * RL_SPLIT_ROWS, rows = min(RL_SPLIT_ROWS, p.N - n0);
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b)
+        if (b < B) sdy[b][lane] = lane < rows ? p.y[(long long)b * p.ldy + n0 + lane] : 0.f;
+    __syncthreads();
+    if (kt == 0 && p.db && lane < rows) {
+        float s = 0.f;
+#pragma unroll
+        for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b)
+            if (b < B) s += sdy[b][lane];
+        p.db[n0 + lane] = p.accumulate ? p.db[n0 + lane] + s : s;
+    }
+    const int k0 = (kt * 64 + lane) * 4;
+    if (k0 >= K) return;
+    const bool full = k0 + 4 <= K;
+    const bool xvec = full && (uintptr_t)p.x % 16 == 0 && p.ldx % 4 == 0, ovec = full && (uintptr_t)p.dw % 16 == 0 && p.ldo % 4 == 0;
+    float xv[T2V_ROWLIN_MAX_ROWS][4];
+#pragma unroll
+    for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+        if (b < B) {
+            const float* xr = p.x + (long long)b * p.ldx + k0;
+            if (xvec) { const float4 v = *(const float4*)xr; xv[b][0] = v.x; xv[b][1] = v.y; xv[b][2] = v.z; xv[b][3] = v.w; }
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[b][e] = k0 + e < K ? xr[e] : 0.f;
+            }
+            if (p.silu) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (k0 + e < K) xv[b][e] = rl_silu(xv[b][e]);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xv[b][e] = 0.f;
+        }
+    }
+    const float alpha = p.alpha;
+    const int acc = p.accumulate;
+    for (int r = 0; r < rows; ++r) {
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < T2V_ROWLIN_MAX_ROWS; ++b) {
+            if (b < B) {
+                const float d = sdy[b][r];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] += d * xv[b][e];
+            }
+        }
+        float* dst = p.dw + (long long)(n0 + r) * p.ldo + k0;
+        if (ovec) {
+            float4 v = make_float4(o[0] * alpha, o[1] * alpha, o[2] * alpha, o[3] * alpha);
+            if (acc) { const float4 old = *(const float4*)dst; v.x += old.x; v.y += old.y; v.z += old.z; v.w += old.w; }
+            *(float4*)dst = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (k0 + e < K) dst[e] = acc ? dst[e] + o[e] * alpha : o[e] * alpha;
+        }
+    }
+}
+
+// out[r][c] = keep(r, c) ? x[r][c] * inv_keep : 0 (+ resid[r][c]) on fp32 rows: the mask of t2v_dropout_bf16 (common.h: one splitmix64 word per quad
+// of the row-major [rows][ncols] matrix, 16 bits per element), for the B-row LoRA branches of the conditioning leaves
+__global__ __launch_bounds__(256) void dropout_f32_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ resid, int ldr, float* __restrict__ out,
+                                                          int ldo, long long total, int ncols, uint32_t thr, float inv_keep, const uint64_t* __restrict__ seed_p,
+                                                          uint32_t site) {
+    const uint64_t key = dropout_key(*seed_p, site);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / ncols;
+        const int c = (int)(i - r * ncols);
+        const uint64_t w = dropout_quad(key, (uint64_t)(i >> 2));
+        float v = dropout_keep16(w, (int)(i & 3), thr) ? x[r * ldx + c] * inv_keep : 0.f;
+        if (resid) v += resid[r * ldr + c];
+        out[r * ldo + c] = v;
+    }
+}
+
+// cos || sin of t * exp(-ln(1e4) i / half) (guidance_style: sin || cos of 1000 t with the (half - 1) divisor), fp32 out: the arithmetic of
+// elementwise.hip's bf16 entry without its last rounding
+__global__ void timestep_embedding_f32_kernel(const void* t, int t_is_f32, int n, int dim, int guidance_style, float* out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int half = dim / 2;
+    if (idx >= n * half) return;
+    const int row = idx / half, i = idx % half;
+    const float tv = t_is_f32 ? ((const float*)t)[row] : (float)((const long long*)t)[row];
+    float c, s;
+    if (guidance_style) {
+        const float freq = expf((float)i * -(logf(10000.0f) / (float)(half - 1)));
+        sincosf(tv * 1000.0f * freq, &s, &c);
+        out[row * dim + i] = s;
+        out[row * dim + half + i] = c;
+    } else {
+        const float freq = expf(-logf(10000.0f) * (float)i / (float)half);
+        sincosf(tv * freq, &s, &c);
+        out[row * dim + i] = c;
+        out[row * dim + half + i] = s;
+    }
+    if ((dim & 1) && i == 0) out[row * dim + dim - 1] = 0.f;
+}
+
 }  // namespace
 
 extern "C" long long t2v_im2col_rows(int mode, int n_img, int h, int w) {
@@ -396,6 +707,154 @@ extern "C" int t2v_repack_conv_f32(const float* w, int N, int C, int taps, int k
         hipLaunchKernelGGL(repack_conv_dgrad_kernel, dim3((C + RP_DC - 1) / RP_DC, (N + RP_DN - 1) / RP_DN), dim3(256), 0, s, w, N, C, taps,
                            (bf16_t*)out, ldo);
     }
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+// ---- B-row linear family: host side ------------------------------------------------------------------------------------------------------
+enum { RL_FWD = 0, RL_BWD = 1, RL_WGRAD = 2 };
+
+// every check of one entry over the WHOLE table, before anything is launched
+static int rowlin_check(const t2v_rowlin_problem* p, int n, int B, int which) {
+    T2V_REQUIRE(p && n >= 1, T2V_EINVAL, "t2v_rowlin: null or empty problem table");
+    T2V_REQUIRE(B >= 1 && B <= T2V_ROWLIN_MAX_ROWS, T2V_EINVAL, "t2v_rowlin: 1 <= B <= T2V_ROWLIN_MAX_ROWS (8) rows");
+    for (int i = 0; i < n; ++i) {
+        const t2v_rowlin_problem& q = p[i];
+        T2V_REQUIRE(q.K > 0 && q.N > 0 && q.y, T2V_EINVAL, "t2v_rowlin: bad problem (K, N > 0; y / dy must be given)");
+        T2V_REQUIRE(q.ldy >= q.N, T2V_ESHAPE, "t2v_rowlin: ldy smaller than N");
+        if (which == RL_FWD) {
+            T2V_REQUIRE(q.x && q.w, T2V_EINVAL, "t2v_rowlin_fwd: null x or w");
+            T2V_REQUIRE(q.ldx >= q.K && q.ldw >= q.K && (!q.res || q.ldr >= q.N), T2V_ESHAPE, "t2v_rowlin_fwd: row stride smaller than the row");
+            T2V_REQUIRE((long long)B * q.K <= RL_LDS_FLOATS, T2V_ESHAPE, "t2v_rowlin_fwd: B * K <= 16384 (the input rows wait in LDS)");
+        } else if (which == RL_BWD) {
+            T2V_REQUIRE(q.w && q.dx && (!q.silu || q.x), T2V_EINVAL, "t2v_rowlin_bwd_data: null w or dx, or silu without the saved pre-activation");
+            T2V_REQUIRE(q.ldw >= q.K && q.ldo >= q.K && (!q.silu || q.ldx >= q.K), T2V_ESHAPE, "t2v_rowlin_bwd_data: row stride smaller than the row");
+            for (int j = 0; j < i; ++j)
+                if (p[j].dx == q.dx)
+                    T2V_REQUIRE(p[j].K == q.K && p[j].ldo == q.ldo && p[j].silu == q.silu && p[j].accumulate == q.accumulate &&
+                                    (!q.silu || (p[j].x == q.x && p[j].ldx == q.ldx)),
+                                T2V_EINVAL, "t2v_rowlin_bwd_data: problems that share dx must agree on K, ldo, g and accumulate");
+        } else {
+            T2V_REQUIRE(q.x && q.dw, T2V_EINVAL, "t2v_rowlin_wgrad: null x or dw");
+            T2V_REQUIRE(q.ldx >= q.K && q.ldo >= q.K, T2V_ESHAPE, "t2v_rowlin_wgrad: row stride smaller than the row");
+        }
+    }
+    return T2V_OK;
+}
+
+static int rowlin_splits(const t2v_rowlin_problem& q) { return (q.N + RL_SPLIT_ROWS - 1) / RL_SPLIT_ROWS; }
+
+extern "C" long long t2v_rowlin_ws_floats(const t2v_rowlin_problem* problems, int n, int B) {
+    if (!problems || n < 1 || B < 1 || B > T2V_ROWLIN_MAX_ROWS) return -1;
+    long long most = 0;
+    for (int c0 = 0; c0 < n; c0 += RL_MAXP) {   // (one launch pair per RL_MAXP problems: the workspace is reused from its start)
+        long long need = 0;
+        for (int i = c0; i < n && i < c0 + RL_MAXP; ++i) {
+            if (problems[i].K <= 0 || problems[i].N <= 0) return -1;
+            need += (long long)rowlin_splits(problems[i]) * B * problems[i].K;
+        }
+        if (need > most) most = need;
+    }
+    return most;
+}
+
+extern "C" int t2v_rowlin_fwd(const t2v_rowlin_problem* problems, int n, int B, void* stream) {
+    const int rc = rowlin_check(problems, n, B, RL_FWD);
+    if (rc != T2V_OK) return rc;
+    for (int c0 = 0; c0 < n; c0 += RL_MAXP) {
+        RowlinTable t = RowlinTable();
+        t.n = n - c0 < RL_MAXP ? n - c0 : RL_MAXP; t.B = B; t.ngroups = 0;
+        int blocks = 0, kmax = 0;
+        for (int i = 0; i < t.n; ++i) {
+            t.p[i] = problems[c0 + i];
+            t.first[i] = blocks;
+            blocks += (t.p[i].N + RL_FWD_ROWS - 1) / RL_FWD_ROWS;
+            if (t.p[i].K > kmax) kmax = t.p[i].K;
+        }
+        t.first[t.n] = blocks;
+        hipLaunchKernelGGL(rowlin_fwd_kernel, dim3((unsigned)blocks), dim3(256), (size_t)B * kmax * sizeof(float), (hipStream_t)stream, t);
+        T2V_CHECK_LAUNCH();
+    }
+    return T2V_OK;
+}
+
+extern "C" int t2v_rowlin_bwd_data(const t2v_rowlin_problem* problems, int n, int B, float* ws, long long ws_floats, void* stream) {
+    const int rc = rowlin_check(problems, n, B, RL_BWD);
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(ws && (uintptr_t)ws % 4 == 0, T2V_EINVAL, "t2v_rowlin_bwd_data: null workspace");
+    T2V_REQUIRE(ws_floats >= t2v_rowlin_ws_floats(problems, n, B), T2V_ESHAPE, "t2v_rowlin_bwd_data: workspace smaller than t2v_rowlin_ws_floats");
+    for (int c0 = 0; c0 < n; c0 += RL_MAXP) {
+        RowlinTable t = RowlinTable();
+        t.n = n - c0 < RL_MAXP ? n - c0 : RL_MAXP; t.B = B; t.ngroups = 0;
+        int blocks = 0, kmax = 0;
+        long long off = 0;
+        for (int i = 0; i < t.n; ++i) {
+            t2v_rowlin_problem& q = t.p[i];
+            q = problems[c0 + i];
+            for (int j = 0; j < c0; ++j)   // a dx an earlier launch pair of this call already wrote: its sums are added to, g(pre) distributes
+                if (problems[j].dx == q.dx) q.accumulate = 1;
+            const int vec = q.w_bf16 ? 8 : 4, ktiles = ((q.K + vec - 1) / vec + 63) / 64;
+            t.nsplit[i] = rowlin_splits(q);
+            t.ws_off[i] = off;
+            t.first[i] = blocks;
+            blocks += t.nsplit[i] * ktiles;
+            off += (long long)t.nsplit[i] * B * q.K;
+            bool seen = false;
+            for (int j = 0; j < i; ++j) seen = seen || t.p[j].dx == q.dx;
+            if (!seen) { t.lead[t.ngroups++] = i; if (q.K > kmax) kmax = q.K; }
+        }
+        t.first[t.n] = blocks;
+        hipLaunchKernelGGL(rowlin_bwd_partial_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, t, ws);
+        T2V_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rowlin_bwd_finish_kernel, dim3((unsigned)((B * kmax + 255) / 256), (unsigned)t.ngroups), dim3(256), 0, (hipStream_t)stream, t,
+                           (const float*)ws);
+        T2V_CHECK_LAUNCH();
+    }
+    return T2V_OK;
+}
+
+extern "C" int t2v_rowlin_wgrad(const t2v_rowlin_problem* problems, int n, int B, void* stream) {
+    const int rc = rowlin_check(problems, n, B, RL_WGRAD);
+    if (rc != T2V_OK) return rc;
+    for (int c0 = 0; c0 < n; c0 += RL_MAXP) {
+        RowlinTable t = RowlinTable();
+        t.n = n - c0 < RL_MAXP ? n - c0 : RL_MAXP; t.B = B; t.ngroups = 0;
+        int blocks = 0;
+        for (int i = 0; i < t.n; ++i) {
+            t.p[i] = problems[c0 + i];
+            t.first[i] = blocks;
+            blocks += rowlin_splits(t.p[i]) * (((t.p[i].K + 3) / 4 + 63) / 64);
+        }
+        t.first[t.n] = blocks;
+        hipLaunchKernelGGL(rowlin_wgrad_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, t);
+        T2V_CHECK_LAUNCH();
+    }
+    return T2V_OK;
+}
+
+extern "C" int t2v_timestep_embedding_f32(const void* t, int t_is_f32, int n, int dim, int guidance_style, float* out, void* stream) {
+    T2V_REQUIRE(t && out && n > 0 && dim >= 4, T2V_EINVAL, "t2v_timestep_embedding_f32");
+    const long long total = (long long)n * (dim / 2);
+    hipLaunchKernelGGL(timestep_embedding_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, t_is_f32, n, dim,
+                       guidance_style, out);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_dropout_f32(const float* x, int ldx, const float* resid, int ldr, float* out, int ldo, long long rows, int ncols, float p,
+                               const void* seed, unsigned site, void* stream) {
+    T2V_REQUIRE(x && out && seed && rows > 0 && ncols > 0, T2V_EINVAL, "t2v_dropout_f32: null pointer / empty");
+    T2V_REQUIRE(p >= 0.f && p < 1.f - 1.f / 65536.f, T2V_EINVAL, "t2v_dropout_f32: p must be in [0, 1 - 2^-16)");
+    T2V_REQUIRE(ncols % 2 == 0 && ldx >= ncols && ldo >= ncols && (!resid || ldr >= ncols), T2V_ESHAPE,
+                "t2v_dropout_f32: even column count, row strides >= ncols");
+    const double t = (double)p * 4294967296.0;
+    const uint32_t thr = (t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t) >> 16;
+    const float inv_keep = 65536.0f / (65536.0f - (float)thr);
+    const long long total = rows * ncols;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(dropout_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, resid, ldr, out, ldo, total, ncols, thr, inv_keep,
+                       (const uint64_t*)seed, (uint32_t)site);
     T2V_CHECK_LAUNCH();
     return T2V_OK;
 }

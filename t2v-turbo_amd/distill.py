@@ -122,8 +122,10 @@ def distill_step(unet, teacher_unet, solver, noise_scheduler, latents, prompt_em
 
     def student_native(x, ts, grad):
         """Student network on the gradient engine; the conditioning branch (B rows) through torch, with or without grad."""
-        with torch.set_grad_enabled(grad), autocast():
-            emb_all = unet.conditioning_emb_all(ts, fps, w_embedding)
+        emb_all = None      # (the engine owns the conditioning branch: UNetModel.native_conditioning)
+        if not eng.owns_conditioning(x.shape[0]):
+            with torch.set_grad_enabled(grad), autocast():
+                emb_all = unet.conditioning_emb_all(ts, fps, w_embedding)
         y = eng.forward_tape(x.float(), ts, prompt_embeds.float(), fps, w_embedding, None, emb_all=emb_all)
         return y, emb_all
 
@@ -191,7 +193,8 @@ def distill_step(unet, teacher_unet, solver, noise_scheduler, latents, prompt_em
             # native student backward: token-row LoRA gradients straight into the flat buffer (added to what the reward /
             # conditioning branch put there), then the B-row conditioning branch through torch
             eng.backward(noise_pred.grad, flat_grad=grad_sync.flat, accumulate=True, grad_sync=grad_sync)
-            emb_all.backward(eng.d_emb_all.to(emb_all.dtype))
+            if emb_all is not None:
+                emb_all.backward(eng.d_emb_all.to(emb_all.dtype))
         _mark("backward")
         if grad_sync is not None:
             grad_sync.all_reduce_mean()

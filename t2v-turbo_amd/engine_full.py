@@ -14,7 +14,8 @@ The tape and the data gradients are the gradient engine's (engine_unet_bwd.py). 
 
 into one fp32 tensor per parameter (``plan["fgrads"]``), which the autograd bridge (unet3d._NativeStudentFull) hands to torch.
 The conditioning branch (time / fps / guidance MLPs, ``emb_layers``: B rows) stays with torch autograd behind ``emb_all``, as in LoRA
-training.  The weights change every optimizer step: the Packer re-fills its packs IN PLACE (``Packer.refresh``), so the recorded launch
+training — or, with ``native_conditioning`` on, runs on the engine as well (t2v_rowlin_* on the live fp32 parameters, no packs: nothing
+below that refreshes packs sees those leaves).  The weights change every optimizer step: the Packer re-fills its packs IN PLACE (``Packer.refresh``), so the recorded launch
 lists — raw device pointers — stay valid and nothing is re-recorded.  Every plan (input signature) owns its Packer and is refreshed on
 its own, when its packs are behind the parameters.
 
@@ -57,7 +58,8 @@ class FullTrainMixin:
 
     @staticmethod
     def conditioning_module_ids(model):
-        """Modules of the B-row conditioning branch (their parameters' gradients are torch's, through ``emb_all``)."""
+        """Modules of the B-row conditioning branch (their parameters' gradients are torch's, through ``emb_all``, unless the engine
+        owns the branch: ``UNetGradEngine.native_conditioning``)."""
         from .unet3d import ResBlock
         cond = set()
         for name in ("time_embed", "fps_embedding", "time_cond_proj", "motion_cond_proj", "combine_proj"):
@@ -70,9 +72,10 @@ class FullTrainMixin:
         return cond
 
     @classmethod
-    def engine_parameters(cls, model):
-        """Every parameter of ``model`` the engine differentiates, in ``named_parameters`` order."""
-        cond = cls.conditioning_module_ids(model)
+    def engine_parameters(cls, model, conditioning=False):
+        """Every parameter of ``model`` the engine differentiates, in ``named_parameters`` order.  ``conditioning``: the engine owns the
+        B-row branch too (``UNetGradEngine.native_conditioning``) — then that is every parameter."""
+        cond = set() if conditioning else cls.conditioning_module_ids(model)
         out, seen = [], set()
         for mod in model.modules():
             if id(mod) in cond:

@@ -18,7 +18,8 @@ The frozen base weights are packed once.  The LoRA tensors change every optimize
 (D forward / D data-gradient / U / U^T, bf16, zero-padded to rank 64) are re-laid from ONE flat fp32 copy of the trainable
 parameters by ONE indexed-gather launch per step (``t2v_gather_f32``); one more gather carries every weight gradient from the
 GEMM output layout into the flat gradient buffer (``dist.FlatGradSync``) that the all-reduce and ``optim.FlatAdamW`` work
-on.  Leaves of the conditioning branch (time / fps / guidance MLPs, ``emb_layers``: M = B rows) stay in torch autograd; the
+on.  Leaves of the conditioning branch (time / fps / guidance MLPs, ``emb_layers``: M = B rows) stay in torch autograd (unless
+``native_conditioning`` puts them on the engine too: engine_unet_bwd._conditioning_t, fp32 row kernels on the live tensors); the
 engine hands back d(loss)/d(emb_all), column sums of the ResBlock gradients taken as one more GEMM against a clip-indicator
 row.  A train-mode student's dropouts (LoRA branch, temporal conv blocks) are counter-based masks (``t2v_dropout_bf16``):
 a function of (step seed, site, element), applied in the forward and regenerated in the backward — not torch's random stream.
@@ -88,9 +89,12 @@ class LoraTrainMixin:
     def training_lora(self):
         return self.lora_params is not None
 
-    def engine_leaves(self):
-        """Injected leaves whose gradients the engine computes (token-row leaves; the B-row conditioning branch is torch's), in
-        registration order.  Cached per binding: the module route asks on every call, and a walk in ``modules()`` order costs ms."""
+    def engine_leaves(self, conditioning=False):
+        """Injected leaves whose gradients the engine computes (token-row leaves; the B-row conditioning branch is torch's unless the
+        engine owns it: ``conditioning``), in registration order.  Cached per binding: the module route asks on every call, and a walk
+        in ``modules()`` order costs ms."""
+        if conditioning:
+            return self.engine_leaves() + self.cond_lora_leaves()
         cached = getattr(self, "_engine_leaves", None)
         if cached is not None and all(is_lora_leaf(mod) for mod in cached[:4]):
             return cached
@@ -129,6 +133,9 @@ class LoraTrainMixin:
             rp, ce, npad = _pad(r, RP), _pad(cin, 64), _pad(n_out, 64)
             n_lp += 2 * rp * taps * ce + n_out * rp * (2 if self.fuse_lora else 1) + rp * npad + (taps * rp) ** 2 * (taps > 1)
             n_e += n_out * rp + taps * rp * ce
+        if getattr(self, "_cond_owned", False):      # the B-row conditioning leaves (engine_unet_bwd._conditioning_t): slots in the parameters' own layout
+            for mod in self.cond_lora_leaves():
+                n_e += mod.lora_up.weight.numel() + mod.lora_down.weight.numel()
         self.lp = torch.zeros(n_lp, dtype=self.adt, device=dev)
         self.lp_idx = torch.full((n_lp,), -1, dtype=torch.int32, device=dev)
         self.lp_used = 0
@@ -138,6 +145,7 @@ class LoraTrainMixin:
         self.src_flat = torch.empty(self.lora_numel + 1, dtype=torch.float32, device=dev)
         self.one_idx = self.lora_numel  # src_flat[-1] == 1: the constant entries of an operand (the selection packs) index it
         self._groups = {}
+        self._cond_slots = {}
         self._packs_key = None
         self._refresh_src()
 
@@ -538,6 +546,9 @@ class LoraTrainMixin:
 
     def conditioning_index(self):
         """int64 positions (flat-buffer order) of the LoRA tensors whose gradients torch computes (the B-row conditioning branch)."""
+        last = getattr(self, "_last", None)
+        if last is not None and last.get("cond") is not None:     # the engine owns the branch: nothing is left to torch
+            return torch.zeros(0, dtype=torch.int64, device=self.E.device)
         idx = getattr(self, "_cond_idx", None)
         if idx is None or idx[0] is not self.lora_params:
             parts = [torch.arange(self.lora_off[id(p)], self.lora_off[id(p)] + p.numel()) for p in self.conditioning_parameters()]

@@ -74,8 +74,37 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         if self.checkpoint_blocks != before:
             self.plans.clear()                      # recorded launch lists are specific to the mode
 
+    # The B-row conditioning branch (time / fps / guidance MLPs, every ResBlock's emb_layers) on the engine instead of torch autograd:
+    # recorded from the step's real inputs with the fp32 row kernels of csrc/full_grad.hip (t2v_rowlin_*), which read the master
+    # parameters in place — no packs, nothing to refresh — and its backward, run from ``plan["d_emb"]``, ends the recorded backward
+    # list.  Opt-in: T2V_NATIVE_COND=1 (read when the engine is built), ``UNetModel.native_conditioning`` = True / False per module,
+    # or the attribute below on an engine (a change drops the recorded plans).  Full fine-tuning and LoRA training; a batch of more
+    # than T2V_ROWLIN_MAX_ROWS clips (or input rows beyond the forward kernel's LDS) keeps the torch branch for that plan.
+    _cond_set = None
+
+    @property
+    def native_conditioning(self):
+        return self._cond_env if self._cond_set is None else self._cond_set
+
+    @native_conditioning.setter
+    def native_conditioning(self, on):
+        """True / False, or None: back to what T2V_NATIVE_COND said when the engine was built."""
+        before = self.native_conditioning
+        self._cond_set = None if on is None else bool(on)
+        if self.native_conditioning != before:
+            self.plans.clear()
+            if self.training_full:      # the conditioning leaves join / leave the parameters the engine differentiates
+                self.bind_full(self.engine_parameters(self.model, conditioning=self.native_conditioning))
+
+    def owns_conditioning(self, batch):
+        """The engine runs the conditioning branch of a training plan with ``batch`` clips itself (then ``forward_tape`` takes no emb_all)."""
+        if not (self.native_conditioning and self.trains and batch <= nt.ROWLIN_MAX_ROWS):
+            return False
+        return batch * self._cond_linears()[2] <= nt.ROWLIN_LDS_FLOATS     # (t2v_rowlin_fwd keeps a problem's B x K input rows in LDS)
+
     def __init__(self, model, ops):
         super().__init__(model, ops)
+        self._cond_env = os.environ.get("T2V_NATIVE_COND", "0") == "1"
         # GroupNorm statistics of the forward from the producing GEMMs' epilogues (t2v_gemm colstat_out -> t2v_gn_stats_cs), as on
         # the inference engine; the tape keeps (mean, rstd) for the backward either way.  T2V_FUSE_GN_TRAIN=0: statistics pass
         # over the tensor (t2v_gn_stats).
@@ -109,7 +138,9 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         the caller in torch (``conditioning_torch``) so that autograd owns that branch's 27 tiny leaves."""
         m = self.model
         assert x.dim() == 5 and context is not None
-        assert (emb_all is not None) == self.trains, "emb_all is given exactly when LoRA tensors / the base weights are bound for training"
+        owns = self.owns_conditioning(x.shape[0])
+        assert (emb_all is not None) == (self.trains and not owns), \
+            "emb_all is given exactly when LoRA tensors / the base weights are bound for training and the engine does not own the conditioning branch"
         # (full fine-tuning: every parameter moves every step — the packs are re-filled in place instead of dropping the plans)
         if not self.training_full:
             self._check_weights(m, self.lora_ids if self.training_lora else ())
@@ -120,6 +151,9 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
                None if timestep_cond is None else tuple(timestep_cond.shape),
                None if motion_cond is None else tuple(motion_cond.shape), x.device, self.training_lora, self.training_full)
         plan = self.plans.get(key)
+        if plan is not None and owns and plan.get("cond_ptrs") != self._cond_ptrs():
+            del self.plans[key]                     # a conditioning parameter was re-homed: its recorded launches read the old storage
+            plan = None
         if dropping:  # one seed per forward; the backward regenerates the same masks from it
             self._seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
         if plan is None:
@@ -131,8 +165,9 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         else:
             st = plan["static"]
             self._load_inputs(st, x, timesteps, context, fps, timestep_cond, motion_cond)
-            if emb_all is not None:
-                st["emb_all"].copy_(emb_all.detach())
+            if self.trains:
+                if emb_all is not None:
+                    st["emb_all"].copy_(emb_all.detach())
                 if self.training_lora:
                     self.refresh_lora_packs()
                 else:
@@ -224,16 +259,25 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         if self.training_lora:
             # frozen base weights are packed as they are; the LoRA branch runs as its own GEMMs on per-step operand packs
             self.pk = Packer(self.adt, x.device, merge_lora=False)
+            self._cond_owned = emb_all is None      # (the conditioning leaves' gradient slots are part of the arena then)
             self._lora_begin()
-            st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
-            plan["d_emb"] = torch.zeros_like(st["emb_all"])
+            if emb_all is not None:
+                st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
+                plan["d_emb"] = torch.zeros_like(st["emb_all"])
+            else:
+                plan["d_emb"] = torch.zeros(B, self._emb_table()[1], dtype=torch.float32, device=x.device)
+                plan["cond_ptrs"] = self._cond_ptrs()
             st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
             self.seed_t = st["seed"]
         if self.training_full:
             # plain leaves on packs of the current weights (re-filled in place per step: Packer.refresh); one fp32 gradient per parameter
             self.pk = Packer(self.adt, x.device)
-            st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
-            plan["d_emb"] = torch.zeros_like(st["emb_all"])
+            if emb_all is not None:
+                st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
+                plan["d_emb"] = torch.zeros_like(st["emb_all"])
+            else:   # the engine owns the conditioning branch: emb_all is made by the recorded forward, d_emb consumed by the recorded backward
+                plan["d_emb"] = torch.zeros(B, self._emb_table()[1], dtype=torch.float32, device=x.device)
+                plan["cond_ptrs"] = self._cond_ptrs()
             plan["fgrads"] = {}
             st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
             self.seed_t = st["seed"]
@@ -572,12 +616,205 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         """Embedding / context branch of UNetEngine._forward (no dependence on the latents: no tape)."""
         self._context(st)
         self._ctx_f = None
-        if self.trains:  # the M = B-row branch belongs to torch autograd (engine_lora.py / engine_full.py); its result is an input
+        if self.trains and "emb_all" not in st:
+            self._conditioning_t(st)
+        elif self.trains:  # the M = B-row branch belongs to torch autograd (engine_lora.py / engine_full.py); its result is an input
             width = self._emb_table()[1]
             assert st["emb_all"].shape == (self.B, width)
             self.emb_all = st["emb_all"]
         else:
             self._embedding(st)
+
+    # ---- the conditioning branch on the engine (``native_conditioning``) ---------------------------------------------------------------
+    def _cond_linears(self):
+        """The Linear leaves of the conditioning branch (injected ones as their wrapper), found once per engine."""
+        got = self.__dict__.get("_cond_lin")
+        if got is None or got[0] is not self.full_params or got[1] is not self.lora_params:
+            m = self.model
+            mods = [getattr(m, n, None) for n in ("time_cond_proj", "motion_cond_proj", "combine_proj")]
+            mods += [m.time_embed[0], m.time_embed[2]] + ([m.fps_embedding[0], m.fps_embedding[2]] if m.fps_cond else [])
+            mods += [rb.emb_layers[1] for rb in self._emb_table()[0]]
+            mods = [mod for mod in mods if mod is not None]
+            params = [p for mod in mods for sub in mod.modules() for p in sub._parameters.values() if p is not None]
+            kmax = max((mod.linear if is_lora_leaf(mod) else mod).weight.shape[1] for mod in mods)
+            got = self._cond_lin = (self.full_params, self.lora_params, mods, params, kmax)
+        return got[2:]
+
+    def _cond_ptrs(self):
+        return tuple(p.data_ptr() for p in self._cond_linears()[1])
+
+    def cond_lora_leaves(self):
+        return [mod for mod in self._cond_linears()[0] if is_lora_leaf(mod)]
+
+    def _conditioning_t(self, st):
+        """UNetEngine._embedding in fp32 on the live parameters (t2v_rowlin_fwd), from the static inputs ts / fps / tc / mc.  Keeps the B-row
+        activations the backward needs in the plan (a few kilobytes, outside the pool: a checkpointed block never discards them).  An
+        injected leaf runs its LoRA branch as the same entry three times — t = f(x) D^T, u = s t U^T (+ res), [u = dropout(u) (+ res),]
+        y = f(x) W^T + b + u (utils/lora.py:45-50) — and gets its gradient slots at the bottom of the arena E."""
+        m, ops = self.model, self.ops
+        B, mc, dev = self.B, m.model_channels, st["x"].device
+        blocks, width = self._emb_table()
+        c = {"keep": []}
+
+        def new(cols):
+            t = torch.empty(B, cols, dtype=torch.float32, device=dev)
+            c["keep"].append(t)
+            return t
+
+        def f32(t):
+            if t.dtype == torch.float32:
+                return t
+            out = new(t.shape[1])
+            ops.cast(t, out)
+            return out
+
+        def lin_table(items, per_frame=False):
+            """items: (x, module, y or None, silu, res) of leaves that do not depend on one another -> their leaf records (with "y")."""
+            downs, ups, drops, bases, leaves = [], [], [], [], []
+            # how torch orders the rows a leaf's dropout sees (tests replay the masks): the MLPs run on B rows; the composite path repeats emb
+            # per frame before emb_layers, and one mask per CLIP, as conditioning_emb_all draws it, is every frame's — the "ctx" order, L = 1
+            kind = ("ctx", (B, self.F, 1)) if per_frame else ("rows", None)
+            for x, mod, y, silu, res in items:
+                base = mod.linear if is_lora_leaf(mod) else mod
+                y = new(base.weight.shape[0]) if y is None else y
+                leaf = dict(mod=mod, x=x, silu=silu, y=y)
+                if is_lora_leaf(mod):
+                    assert self.training_lora, "native full fine-tuning of a LoRA-injected network (train the LoRA tensors, or merge them first)"
+                    if not isinstance(mod.selector, nn.Identity):
+                        raise NotImplementedError("native LoRA training: a selector is set on an injected leaf")
+                    D, U = mod.lora_down.weight, mod.lora_up.weight
+                    if id(D) not in self.lora_off or id(U) not in self.lora_off:
+                        raise ValueError("a LoRA leaf's tensors are not in the list given to bind_lora")
+                    n_out, r = U.shape
+                    slots = self._cond_slots.get(id(mod))     # (per arena, like the token-row groups: a closure backend re-runs this forward)
+                    if slots is None:
+                        slots = []
+                        for w, (rows, cols) in ((U, (n_out, r)), (D, (r, D.shape[1]))):   # gradient slots, in the parameter's own layout
+                            off, e = self._e_alloc(rows, cols)
+                            o = self.lora_off[id(w)]
+                            self.g_idx[o:o + w.numel()] = (off + torch.arange(w.numel())).to(dev, torch.int32)
+                            slots.append(e)
+                        self._cond_slots[id(mod)] = slots
+                    leaf["EU"], leaf["ED"] = slots
+                    site = self.drop_site([mod.dropout], *kind)
+                    t, u = new(r), new(n_out)
+                    downs.append(dict(x=x, w=D, y=t, silu=silu))
+                    ups.append(dict(x=t, w=U, y=u, alpha=float(mod.scale), res=None if site else res))
+                    if site:
+                        if n_out % 2:
+                            raise NotImplementedError("native conditioning: dropout on a LoRA branch with an odd number of features")
+                        drops.append((u, res, n_out, site))
+                    leaf.update(t=t, site=site, scale=float(mod.scale))
+                    res = u
+                bases.append(dict(x=x, w=base.weight, bias=base.bias, y=y, silu=silu, res=res))
+                leaves.append(leaf)
+            for table in (downs, ups):
+                if table:
+                    ops.rowlin_fwd(table, B)
+            for u, res, n_out, site in drops:
+                ops.dropout(u, res, u, n_out, site[0], self.seed_t, site[1])
+            ops.rowlin_fwd(bases, B)
+            return leaves
+
+        def lin(x, mod, y=None, silu=False, res=None):
+            leaf = lin_table([(x, mod, y, silu, res)])[0]
+            c[id(mod)] = leaf
+            return leaf["y"]
+
+        c["t_emb"] = new(mc)
+        ops.timestep_embedding_f32(st["ts"], mc, False, c["t_emb"])
+        c["emb_in"] = c["t_emb"]
+        if "tc" in st:
+            c["tc"] = f32(st["tc"])
+            if "mc" in st:   # combine_proj(cat[time_cond_proj(tc), motion_cond_proj(mc)]) + t_emb: the two projections write the halves of one buffer
+                c["mc"] = f32(st["mc"])
+                c["cat"] = new(2 * mc)
+                lin(c["tc"], m.time_cond_proj, y=c["cat"][:, :mc])
+                lin(c["mc"], m.motion_cond_proj, y=c["cat"][:, mc:])
+                c["emb_in"] = lin(c["cat"], m.combine_proj, res=c["t_emb"])
+            else:
+                c["emb_in"] = lin(c["tc"], m.time_cond_proj, res=c["t_emb"])
+        c["e1"] = lin(c["emb_in"], m.time_embed[0])
+        c["emb"] = lin(c["e1"], m.time_embed[2], silu=True)
+        if m.fps_cond:
+            c["f_emb"] = new(mc)
+            ops.timestep_embedding_f32(st["fps"], mc, False, c["f_emb"])
+            c["f1"] = lin(c["f_emb"], m.fps_embedding[0])
+            c["emb"] = lin(c["f1"], m.fps_embedding[2], silu=True, res=c["emb"])
+        # every ResBlock's emb_layers (SiLU -> Linear) as ONE table: problem i writes its column slice of emb_all
+        self.emb_all = new(width)     # (``self.emb_all`` is the NEXT recorded plan's soon: this plan keeps its own)
+        c["layers"] = lin_table([(c["emb"], rb.emb_layers[1], self.emb_all[:, self.emb_off[id(rb)]:self.emb_off[id(rb)] + rb.out_channels], True, None)
+                                 for rb in blocks], per_frame=True)
+        c["blocks"] = blocks
+        self.plan["cond"] = c
+
+    def _conditioning_b(self):
+        """Backward of ``_conditioning_t`` from ``plan["d_emb"]`` (the per-clip column sums the ResBlock backwards left).  Full fine-tuning:
+        every weight and bias gradient by t2v_rowlin_wgrad straight into its slot of the gradient arena.  LoRA training: dU = s dy'^T t and
+        dD = s g^T f(x) (dy' = dy through the forward's mask, g = dy' U) into the leaf's slots of the arena E, from where the one gather of
+        ``lora_grads_into`` carries them to the flat gradient with every other LoRA tensor's.  Data gradients by t2v_rowlin_bwd_data: the
+        frozen base weight and the down-projection of a leaf are two problems that share its dx."""
+        m, ops, c, B = self.model, self.ops, self.plan["cond"], self.B
+        d_all = self.plan["d_emb"]
+        dev = d_all.device
+
+        def new(cols):
+            t = torch.empty(B, cols, dtype=torch.float32, device=dev)
+            c["keep"].append(t)     # (recorded launches hold raw pointers: the plan keeps the tensors alive)
+            return t
+
+        def bwd_data(table):
+            ws = torch.empty(max(ops.rowlin_ws_floats(table, B), 1), dtype=torch.float32, device=dev)
+            c["keep"].append(ws)
+            ops.rowlin_bwd_data(table, B, ws)
+
+        def back(items, pre=None, need_dx=True):
+            """items: (leaf record, dy) of leaves reading the same input -> d(input) = g(pre) * sum of their data gradients (or None)."""
+            if self.training_full:
+                ops.rowlin_wgrad([dict(x=lf["x"], y=dy, silu=lf["silu"], dw=self.fgrad(lf["mod"].weight),
+                                       db=None if lf["mod"].bias is None else self.fgrad(lf["mod"].bias)) for lf, dy in items], B)
+            probs, ups, gs, downs = [], [], [], []
+            for lf, dy in items:
+                mod = lf["mod"]
+                if not is_lora_leaf(mod):
+                    probs.append(dict(w=mod.weight, y=dy))
+                    continue
+                probs.append(dict(w=mod.linear.weight, y=dy))
+                dym = dy
+                if lf["site"]:   # the LoRA branch saw dy through the forward's mask; the base leaf sees dy itself
+                    dym = new(dy.shape[1])
+                    ops.dropout(dy, None, dym, dy.shape[1], lf["site"][0], self.seed_t, lf["site"][1])
+                g = new(lf["t"].shape[1])
+                ups.append(dict(x=lf["t"], y=dym, dw=lf["EU"], alpha=lf["scale"]))
+                gs.append(dict(w=mod.lora_up.weight, y=dym, dx=g))
+                downs.append(dict(x=lf["x"], silu=lf["silu"], y=g, dw=lf["ED"], alpha=lf["scale"]))
+                probs.append(dict(w=mod.lora_down.weight, y=g, alpha=lf["scale"]))
+            if ups:
+                ops.rowlin_wgrad(ups, B)
+                bwd_data(gs)
+                ops.rowlin_wgrad(downs, B)
+            if not need_dx:
+                return None
+            dx = new(probs[0]["w"].shape[1])
+            for q in probs:
+                q.update(dx=dx, x=pre, silu=pre is not None)
+            bwd_data(probs)
+            return dx
+
+        layers = [(lf, d_all[:, self.emb_off[id(rb)]:self.emb_off[id(rb)] + rb.out_channels]) for lf, rb in zip(c["layers"], c["blocks"])]
+        d_emb = back(layers, pre=c["emb"])                          # d(emb): also d(time_embed out) and d(fps_embedding out)
+        if m.fps_cond:
+            d_f1 = back([(c[id(m.fps_embedding[2])], d_emb)], pre=c["f1"])
+            back([(c[id(m.fps_embedding[0])], d_f1)], need_dx=False)
+        d_e1 = back([(c[id(m.time_embed[2])], d_emb)], pre=c["e1"])
+        d_in = back([(c[id(m.time_embed[0])], d_e1)], need_dx="tc" in c)
+        if "mc" in c:
+            mc = m.model_channels
+            d_cat = back([(c[id(m.combine_proj)], d_in)])
+            back([(c[id(m.time_cond_proj)], d_cat[:, :mc])], need_dx=False)
+            back([(c[id(m.motion_cond_proj)], d_cat[:, mc:])], need_dx=False)
+        elif "tc" in c:
+            back([(c[id(m.time_cond_proj)], d_in)], need_dx=False)
 
     def context_kv_t(self, attn, per_frame=False):
         """Training: K / V of ONE cross-attention layer through its own injected to_k / to_v (token-major rows of the text
@@ -633,6 +870,8 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             else:
                 d = fn(d)
         self.entry_bwd(d, dx_out)
+        if self.plan.get("cond") is not None:
+            self._conditioning_b()
         assert not (self.training_full and self._fsaved), "full fine-tuning: a saved leaf input was not taken by any backward"
         if self.training_lora:
             self._seg_emit_down_to(0)   # whatever is left of the arena (and every piece, if some group never finished)

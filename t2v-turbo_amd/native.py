@@ -29,6 +29,18 @@ class WgradProblem(C.Structure):
                 ("ldo", C.c_int), ("R", C.c_int), ("C", C.c_int), ("alpha", C.c_float)]
 
 
+ROWLIN_MAX_ROWS = 8       # T2V_ROWLIN_MAX_ROWS
+ROWLIN_LDS_FLOATS = 16384  # t2v_rowlin_fwd: B * K of a problem (its input rows wait in LDS)
+
+
+class RowlinProblem(C.Structure):
+    """struct t2v_rowlin_problem, field for field (112 bytes)."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("y", C.c_void_p), ("dx", C.c_void_p),
+                ("dw", C.c_void_p), ("db", C.c_void_p), ("K", C.c_int), ("N", C.c_int), ("ldx", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int),
+                ("ldr", C.c_int), ("ldo", C.c_int), ("w_bf16", C.c_int), ("silu", C.c_int), ("accumulate", C.c_int), ("alpha", C.c_float),
+                ("reserved", C.c_int)]
+
+
 ADAMW8_BLOCK = 256       # T2V_ADAMW8_BLOCK
 ADAMW8_F32_STATE = 1     # T2V_ADAMW8_F32_STATE
 
@@ -257,6 +269,13 @@ _SIGS = {
     "t2v_norm_affine_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "t2v_rowlin_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "t2v_rowlin_ws_floats": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
+    "t2v_rowlin_bwd_data": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "t2v_rowlin_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "t2v_dropout_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float,
+                                  C.c_void_p, C.c_uint, C.c_void_p]),
+    "t2v_timestep_embedding_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "t2v_transpose_pad_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong,
                                          C.c_longlong, C.c_void_p]),
     "t2v_dropout_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_float,
@@ -931,6 +950,57 @@ class HipOps:
             ws = self.workspace(chunk[0][0].device)
             self._call("t2v_wgrad_tn_group", C.cast(arr, C.c_void_p), len(chunk), ws.data_ptr(), ws.numel(), keep=arr)
 
+    # ---- the B-row conditioning branch (csrc/full_grad.hip: t2v_rowlin_*) ----------------------------------------------------------
+    # A problem is a dict of tensors and flags, the same for the three entries (see ``t2v_rowlin_problem``): x, w, bias, res, y (fwd: the
+    # output; bwd_data / wgrad: dy), dx, dw, db, silu, accumulate, alpha.  Weights are read in place: an fp32 or bf16 [N, K] tensor.
+    @staticmethod
+    def rowlin_table(problems, B):
+        arr = (RowlinProblem * len(problems))()
+        for d, q in zip(arr, problems):
+            x, w, y = q.get("x"), q.get("w"), q["y"]
+            dx, dw, db, res, bias = q.get("dx"), q.get("dw"), q.get("db"), q.get("res"), q.get("bias")
+            for t in (x, y, dx, res, bias, dw, db):
+                assert t is None or t.dtype == torch.float32
+            assert y.shape[0] == B and (x is None or x.shape[0] == B) and (dx is None or dx.shape[0] == B)
+            d.N = y.shape[1]
+            if w is not None:
+                assert w.dtype in (torch.float32, torch.bfloat16) and w.shape[0] == d.N
+                d.K, d.w, d.ldw, d.w_bf16 = w.shape[1], _p(w), _row_stride(w), int(w.dtype == torch.bfloat16)
+            else:
+                d.K = dw.shape[1]
+            assert all(t is None or t.shape[1] == d.K for t in (x, dx, dw)) and (dw is None or dw.shape[0] == d.N)
+            assert (res is None or tuple(res.shape) == (B, d.N)) and all(t is None or (t.numel() == d.N and t.is_contiguous()) for t in (bias, db))
+            d.x, d.bias, d.res, d.y, d.dx, d.dw, d.db = _p(x), _p(bias), _p(res), _p(y), _p(dx), _p(dw), _p(db)
+            d.ldx, d.ldy = 0 if x is None else _row_stride(x), _row_stride(y)
+            d.ldr = 0 if res is None else _row_stride(res)
+            d.ldo = _row_stride(dx) if dx is not None else (0 if dw is None else _row_stride(dw))
+            d.silu, d.accumulate, d.alpha = int(bool(q.get("silu"))), int(bool(q.get("accumulate"))), float(q.get("alpha", 1.0))
+        return arr
+
+    def rowlin_fwd(self, problems, B):
+        """y = bias + f(x) w^T (+ res) per problem, fp32, B <= 8 rows: one launch for the whole table (t2v_rowlin_fwd)."""
+        arr = self.rowlin_table(problems, B)
+        self._call("t2v_rowlin_fwd", C.cast(arr, C.c_void_p), len(problems), B, keep=arr)
+
+    def rowlin_ws_floats(self, problems, B):
+        arr = self.rowlin_table(problems, B)
+        return int(self.lib.t2v_rowlin_ws_floats(C.cast(arr, C.c_void_p), len(problems), B))
+
+    def rowlin_bwd_data(self, problems, B, ws):
+        """dx (+)= g(x) * sum over the problems naming that dx of dy w (t2v_rowlin_bwd_data); ws: fp32, ``rowlin_ws_floats`` long."""
+        assert ws.dtype == torch.float32 and ws.is_contiguous()
+        arr = self.rowlin_table(problems, B)
+        self._call("t2v_rowlin_bwd_data", C.cast(arr, C.c_void_p), len(problems), B, _p(ws), ws.numel(), keep=arr)
+
+    def rowlin_wgrad(self, problems, B):
+        """dw (+)= alpha dy^T f(x), db (+)= column sums of dy, straight into the gradient tensors (t2v_rowlin_wgrad)."""
+        arr = self.rowlin_table(problems, B)
+        self._call("t2v_rowlin_wgrad", C.cast(arr, C.c_void_p), len(problems), B, keep=arr)
+
+    def timestep_embedding_f32(self, t, dim, guidance_style, out):
+        assert t.dtype in (torch.int64, torch.float32) and t.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
+        self._call("t2v_timestep_embedding_f32", _p(t), 1 if t.dtype == torch.float32 else 0, t.numel(), dim, int(guidance_style), _p(out))
+
     def transpose_pad(self, src, rows, cols, out, batch=1, in_stride=0, out_stride=0):
         """out[b][c][r] = src[b][r][c], zero for rows <= r < roundup(rows, 64) (16-byte accesses; see include/t2v_hip.h)."""
         self._call("t2v_transpose_pad_bf16", _p(src), _row_stride(src), rows, cols, _p(out), _row_stride(out), batch, in_stride,
@@ -938,8 +1008,8 @@ class HipOps:
 
     def dropout(self, x, resid, out, ncols, p, seed, site):
         """out[:, :ncols] = dropout(x[:, :ncols]) (+ resid); mask = f(seed[0], site, row * ncols + col); seed: int64 device tensor."""
-        assert seed.dtype == torch.int64 and x.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
-        self._call("t2v_dropout_bf16", _p(x), _row_stride(x), _p(resid), 0 if resid is None else _row_stride(resid), _p(out),
+        assert seed.dtype == torch.int64 and x.dtype == out.dtype and x.dtype in (torch.bfloat16, torch.float32)
+        self._call("t2v_dropout_bf16" if x.dtype == torch.bfloat16 else "t2v_dropout_f32", _p(x), _row_stride(x), _p(resid), 0 if resid is None else _row_stride(resid), _p(out),
                    _row_stride(out), x.shape[0], ncols, p, _p(seed), site)
 
     def lcm_step(self, x, eps, noise, sa_t, sb_t, c_skip, c_out, sa_p, sb_p, prev, denoised):

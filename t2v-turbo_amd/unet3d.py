@@ -396,10 +396,10 @@ class _NativeStudent(torch.autograd.Function):
     def forward(ctx, x, emb_all, model, args, *leaves):
         eng = model.native_train_engine()
         timesteps, context, fps, tc, mc = args
-        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=emb_all.detach())
+        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=None if emb_all is None else emb_all.detach())
         ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
         ctx.leaves = leaves
-        ctx.x_dtype, ctx.e_dtype = x.dtype, emb_all.dtype
+        ctx.x_dtype, ctx.e_dtype = x.dtype, None if emb_all is None else emb_all.dtype
         return y
 
     @staticmethod
@@ -409,34 +409,39 @@ class _NativeStudent(torch.autograd.Function):
             raise RuntimeError("native student: another grad-mode forward of the same shape ran before this backward "
                                "(the engine keeps one outstanding tape per input shape)")
         eng._last = ctx.plan
+
+        def d_emb():    # (emb_all is None when the engine owns the conditioning branch: its LoRA tensors are among ``leaves`` then)
+            return None if ctx.e_dtype is None else eng.d_emb_all.to(ctx.e_dtype).clone()
         sync = _flat_grad_buffer(eng, ctx.leaves)
         if sync is not None:
             # every LoRA tensor's .grad is already its slot of ONE flat fp32 buffer in bind_lora order (dist.FlatGradSync): the engine
             # adds its weight gradients there in one launch — what 1096 AccumulateGrad nodes would do with 1096 small kernels
             dx = eng.backward(dout, flat_grad=sync.flat, accumulate=True, grad_sync=sync)
-            return (dx.to(ctx.x_dtype), eng.d_emb_all.to(ctx.e_dtype).clone(), None, None, *([None] * len(ctx.leaves)))
+            return (dx.to(ctx.x_dtype), d_emb(), None, None, *([None] * len(ctx.leaves)))
         flat = torch.empty(eng.lora_numel, dtype=torch.float32, device=dout.device)  # fresh: .grad may keep views of it
         dx = eng.backward(dout, flat_grad=flat, accumulate=False)
         grads = []
         for p in ctx.leaves:
             o = eng.lora_off[id(p)]
             grads.append(flat[o:o + p.numel()].view_as(p).to(p.dtype))
-        return (dx.to(ctx.x_dtype), eng.d_emb_all.to(ctx.e_dtype).clone(), None, None, *grads)
+        return (dx.to(ctx.x_dtype), d_emb(), None, None, *grads)
 
 
 class _NativeStudentFull(torch.autograd.Function):
     """UNet forward of the FULL fine-tuning student (train_latent_t2v_turbo_v2.py:669,798-816,1262: every parameter trainable, no LoRA):
     d/d(latents), d/d(emb_all) and the gradient of every parameter outside the B-row conditioning branch come from the native gradient
-    engine (engine_full.py); torch keeps differentiating the conditioning branch behind ``emb_all``."""
+    engine (engine_full.py); torch keeps differentiating the conditioning branch behind ``emb_all``.  With ``native_conditioning`` on
+    the engine owns that branch too: ``emb_all`` is None, the conditioning parameters are among ``params``, and the autograd graph
+    behind the output is this node and the parameters' AccumulateGrad nodes."""
 
     @staticmethod
     def forward(ctx, x, emb_all, model, args, *params):
         eng = model.native_full_engine()
         timesteps, context, fps, tc, mc = args
-        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=emb_all.detach())
+        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=None if emb_all is None else emb_all.detach())
         ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
         ctx.params = params
-        ctx.x_dtype, ctx.e_dtype = x.dtype, emb_all.dtype
+        ctx.x_dtype, ctx.e_dtype = x.dtype, None if emb_all is None else emb_all.dtype
         return y
 
     @staticmethod
@@ -448,7 +453,9 @@ class _NativeStudentFull(torch.autograd.Function):
         eng._last = ctx.plan
         dx = eng.backward(dout)
         grads = [None if (g is None or not p.requires_grad) else g.to(p.dtype) for p, g in zip(ctx.params, eng.full_grads(ctx.params))]
-        return (dx.to(ctx.x_dtype), eng.d_emb_all.to(ctx.e_dtype).clone(), None, None, *grads)
+        # (emb_all is None when the engine owns the conditioning branch: its parameters are among ``params`` then)
+        d_emb = None if ctx.e_dtype is None else eng.d_emb_all.to(ctx.e_dtype).clone()
+        return (dx.to(ctx.x_dtype), d_emb, None, None, *grads)
 
 
 class UNetModel(nn.Module):
@@ -669,6 +676,23 @@ class UNetModel(nn.Module):
             if eng is not None:
                 eng.checkpoint_blocks = self.native_checkpoint
 
+    # ---- the B-row conditioning branch on the native training engines (UNetGradEngine.native_conditioning) -------------------------
+    @property
+    def native_conditioning(self):
+        """None (default): the gradient engines follow T2V_NATIVE_COND [0 | 1], read when an engine is built; True / False: the time / fps /
+        guidance MLPs and every ResBlock's ``emb_layers`` run on the engine (fp32 row kernels on the live parameters, their gradients with
+        every other parameter's, or the LoRA tensors' in the flat arena) / stay with torch autograd behind ``emb_all``, for the engines of
+        this module: full fine-tuning and LoRA training.  Setting it later goes through the engines' setter, which drops their recorded plans."""
+        return self.__dict__.get("_native_conditioning")
+
+    @native_conditioning.setter
+    def native_conditioning(self, on):
+        self.__dict__["_native_conditioning"] = None if on is None else bool(on)
+        for slot in ("full", "grad", "enc"):
+            eng = getattr(self._engine_box, slot, None)
+            if eng is not None:
+                eng.native_conditioning = self.native_conditioning
+
     # ---- native FULL fine-tuning (every parameter trainable, no LoRA: train_latent_t2v_turbo_v2.py) ---------------------------------
     native_full = os.environ.get("T2V_NATIVE_FULL", "1") == "1"
 
@@ -680,7 +704,8 @@ class UNetModel(nn.Module):
                 from .native import HipOps as make_ops
             eng = UNetGradEngine(self, make_ops())
             eng.checkpoint_blocks = self.native_checkpoint
-            eng.bind_full(eng.engine_parameters(self))
+            eng.native_conditioning = self.native_conditioning
+            eng.bind_full(eng.engine_parameters(self, conditioning=eng.native_conditioning))
             self._engine_box.full = eng
         return self._engine_box.full
 
@@ -692,7 +717,7 @@ class UNetModel(nn.Module):
         if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
             raise RuntimeError("native full fine-tuning: gradients flow to the latents and the parameters only")
         eng = self.native_full_engine()
-        emb_all = self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
+        emb_all = None if eng.owns_conditioning(x.shape[0]) else self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
         args = (timesteps, context, fps, timestep_cond, motion_cond)
         return _NativeStudentFull.apply(x, emb_all, self, args, *eng.full_params)
 
@@ -710,6 +735,7 @@ class UNetModel(nn.Module):
                 from .native import HipOps as make_ops
             eng = UNetGradEngine(self, make_ops())
             eng.checkpoint_blocks = self.native_checkpoint
+            eng.native_conditioning = self.native_conditioning
             eng.bind_lora(lora.lora_parameters(self))
             setattr(self._engine_box, slot, eng)
         return getattr(self._engine_box, slot)
@@ -727,11 +753,12 @@ class UNetModel(nn.Module):
             raise RuntimeError('native_mode = "train": only LoRA tensors may require grad (the base weights are frozen packs)')
         if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
             raise RuntimeError('native_mode = "train": gradients flow to the latents and the LoRA tensors only')
-        emb_all = self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
+        owns = eng.owns_conditioning(x.shape[0])
+        emb_all = None if owns else self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
         args = (timesteps, context, fps, timestep_cond, motion_cond)
         if not grad:
             return eng.forward_tape(x, *args, emb_all=emb_all)
-        leaves = [p for mod in eng.engine_leaves() for p in (mod.lora_up.weight, mod.lora_down.weight)]
+        leaves = [p for mod in eng.engine_leaves(conditioning=owns) for p in (mod.lora_up.weight, mod.lora_down.weight)]
         return _NativeStudent.apply(x, emb_all, self, args, *leaves)
 
     def _embedding(self, timesteps, fps, timestep_cond, motion_cond):

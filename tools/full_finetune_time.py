@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--train", type=int, default=1, help="train mode (the TemporalConvBlock dropouts live), as the v2 script runs its student")
+    ap.add_argument("--cond", type=int, default=-1, help="1 / 0: UNetModel.native_conditioning on / off (-1: leave it to T2V_NATIVE_COND)")
     ap.add_argument("--native", type=int, default=1, help="0: the torch composite path over ATen kernels (native_mode = 'off'), for comparison")
     args = ap.parse_args()
     import bench
@@ -35,12 +36,14 @@ def main():
     m.train() if args.train else m.eval()
     if not args.native:
         m.native_mode = "off"
+    if args.cond >= 0:
+        m.native_conditioning = bool(args.cond)
     x, ctx, tc = bench.synth_inputs(dev, torch.float32)
     x = x[:, :, :args.frames].contiguous()
     ts = torch.tensor([999], device=dev)
     params = [p for p in m.parameters()]
-    out = {"frames": args.frames, "train_mode": bool(args.train), "params_m": round(sum(p.numel() for p in params) / 1e6, 1)}
-    times = []
+    out = {"frames": args.frames, "native_conditioning": args.cond, "train_mode": bool(args.train), "params_m": round(sum(p.numel() for p in params) / 1e6, 1)}
+    times, hosts = [], []
     torch.cuda.reset_peak_memory_stats()
     for step in range(args.steps + 1):   # step 0 records the two launch lists
         for p in params:
@@ -53,6 +56,7 @@ def main():
             y = m(x, ts, context=ctx, fps=16, timestep_cond=tc)
         loss = y.float().pow(2).mean()
         loss.backward()
+        t_host = time.perf_counter()      # the launching thread is done issuing the step; the device may still be running it
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         with torch.no_grad():
@@ -60,6 +64,7 @@ def main():
                 p.add_(p.grad, alpha=-1e-6)
         torch.cuda.synchronize()
         times.append((t1 - t0) * 1e3)
+        hosts.append((t_host - t0) * 1e3)
         if step == 0:
             out["all_grads_present"] = all(p.grad is not None for p in params)
             out["all_grads_finite"] = all(bool(torch.isfinite(p.grad).all()) for p in params)
@@ -77,7 +82,7 @@ def main():
             best = min(best, ((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
         out["pack_refresh_ms"] = {"host_issue": round(best[0], 2), "until_device_done": round(best[1], 2), "packs": len(eng.pk)}
     out.update(path="native gradient engine" if args.native else "torch composite (ATen kernels)", record_ms=round(times[0], 1),
-               step_ms=[round(t, 1) for t in times[1:]], loss=float(loss.detach()), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1))
+               step_ms=[round(t, 1) for t in times[1:]], host_ms=[round(t, 1) for t in hosts[1:]], loss=float(loss.detach()), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1))
     if args.native:
         eng = m._engine_box.full
         plan = next(iter(eng.plans.values()))
