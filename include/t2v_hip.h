@@ -460,6 +460,27 @@ int t2v_attn_temporal_bwd(const void* q, int ldq, const void* k, int ldk, const 
                           const float* dprobs, void* dq, int ldq2, void* dk, int ldk2, void* dv, int ldv2, int n_clips, int frames,
                           int hw, int heads, float scale, void* stream);
 
+/* ---------------------------------------------------------------- motion-prior loss on the recorded probabilities
+ * The loss between the temporal attention probabilities of two forwards (utils/common_utils.py:446-478: sort, scatter, boolean
+ * gather, MSE) and its gradient w.r.t. the differentiated ones, for every recorded layer in ONE launch pair.
+ * Per problem (layer) p with rows_p rows of n values: an entry is SELECTED when fewer than rank_k entries of its row beat it, where
+ * "beat" is a larger ref, or an equal ref at a higher index (the last rank_k places of a stable ascending sort);
+ *   loss[p] = sum over the selected entries of (gen - ref)^2 / (rows_p * rank_k)
+ *   d_gen   = alpha * 2 / (rows_p * rank_k) * (gen - ref) on the selected entries, 0 elsewhere (every element is written).
+ * 1 <= n <= 64, 1 <= rank_k <= n (T2V_ESHAPE), 1 <= n_problems <= T2V_RANK_LOSS_MAX (T2V_EINVAL).  ws: one float per workgroup,
+ * ws_floats >= sum over p of ceil(rows_p / (T2V_RANK_LOSS_WG_LANES / nh)), nh = the power of two >= n (T2V_ESHAPE below that).
+ * The sums are taken in a fixed order (per-workgroup partials, then one small launch): same inputs, same bits. */
+#define T2V_RANK_LOSS_MAX 16
+#define T2V_RANK_LOSS_WG_LANES 2048
+typedef struct t2v_rank_loss_problem {
+    const float* ref;   /* [rows, n] contiguous: reference probabilities                    */
+    const float* gen;   /* [rows, n] contiguous                                             */
+    float* d_gen;       /* [rows, n] out, EVERY element written (zeros where not selected)  */
+    long long rows;
+} t2v_rank_loss_problem;
+int t2v_rank_loss(const t2v_rank_loss_problem* p, int n_problems, int n, int rank_k, float alpha, float* ws, long long ws_floats,
+                  float* loss /* [n_problems] */, void* stream);
+
 /* ---------------------------------------------------------------- optimizer / EMA over flat fp32 buffers
  * Replace bitsandbytes AdamW8bit / torch AdamW on the LoRA tensors (train_t2v_turbo_v1_lora.py:765-803),
  * accelerator.clip_grad_norm_ (:1193) and update_ema (utils/common_utils.py:307-319).

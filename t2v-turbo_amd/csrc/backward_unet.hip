@@ -548,6 +548,77 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_mfma_kernel(const bf16_
     }
 }
 
+// ---- top-k selection loss of the motion-prior score (motion_prior.compute_temp_loss_fused; utils/common_utils.py:446-478) --------
+// Up to T2V_RANK_LOSS_MAX problems (the recorded temporal layers) in one launch pair.  One lane per element: a row of n values sits
+// in a group of nh = 2^lg >= n neighbouring lanes, 64 / nh rows per wave; the rank of an element among its row — how many entries
+// beat it: a larger ref, or an equal ref at a higher index, i.e. its place from the end of a stable ascending sort — is n shuffles
+// inside the lane group.  A workgroup owns T2V_RANK_LOSS_WG_LANES / nh consecutive rows of ONE problem (first_block[]: prefix of the
+// workgroups per problem) and leaves the sum of its selected (gen - ref)^2 in ws[block]; the second launch adds each problem's
+// partials in a fixed order.  No atomics: the same inputs give the same bits.
+constexpr int RL_ITERS = T2V_RANK_LOSS_WG_LANES / 256;
+struct RankLossGroup {
+    t2v_rank_loss_problem p[T2V_RANK_LOSS_MAX];
+    float coef[T2V_RANK_LOSS_MAX];      // alpha * 2 / (rows * rank_k)
+    double inv_count[T2V_RANK_LOSS_MAX];  // 1 / (rows * rank_k)
+    int first_block[T2V_RANK_LOSS_MAX + 1];
+    int n_problems;
+};
+__global__ __launch_bounds__(256) void rank_loss_kernel(const RankLossGroup g, int n, int lg, int rank_k, float* __restrict__ ws) {
+    __shared__ float sh[4];
+    const int bid = blockIdx.x;
+    int i = 0;
+    while (i + 1 < g.n_problems && bid >= g.first_block[i + 1]) ++i;   // block-uniform
+    const float* __restrict__ ref = g.p[i].ref;
+    const float* __restrict__ gen = g.p[i].gen;
+    float* __restrict__ d_gen = g.p[i].d_gen;
+    const long long rows = g.p[i].rows;
+    const float coef = g.coef[i];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nh = 1 << lg, rpw = 64 >> lg;           // lanes per row, rows per wave
+    const int j = lane & (nh - 1), first = lane - j;  // my element, the first lane of my row
+    const long long row0 = (long long)(bid - g.first_block[i]) * (T2V_RANK_LOSS_WG_LANES >> lg) + wave * rpw + (lane >> lg);
+    float r[RL_ITERS], d[RL_ITERS];
+#pragma unroll
+    for (int it = 0; it < RL_ITERS; ++it) {   // all loads first: two coalesced streams
+        const long long row = row0 + (long long)it * 4 * rpw;
+        const bool ok = row < rows && j < n;
+        r[it] = ok ? ref[row * n + j] : 0.f;
+        d[it] = ok ? gen[row * n + j] - r[it] : 0.f;
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int it = 0; it < RL_ITERS; ++it) {
+        const long long row = row0 + (long long)it * 4 * rpw;
+        int beat = 0;
+        for (int t = 0; t < n; ++t) {   // (every lane of the wave takes part in every shuffle)
+            const float o = __shfl(r[it], first + t, 64);
+            beat += (o > r[it] || (o == r[it] && t > j)) ? 1 : 0;
+        }
+        if (row < rows && j < n) {
+            const bool sel = beat < rank_k;
+            d_gen[row * n + j] = sel ? coef * d[it] : 0.f;
+            acc += sel ? d[it] * d[it] : 0.f;
+        }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) sh[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[bid] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ __launch_bounds__(256) void rank_loss_final_kernel(const RankLossGroup g, const float* __restrict__ ws, float* __restrict__ loss) {
+    __shared__ double sh[256];
+    const int i = blockIdx.x;
+    double a = 0.0;
+    for (int b = g.first_block[i] + threadIdx.x; b < g.first_block[i + 1]; b += 256) a += (double)ws[b];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[i] = (float)(sh[0] * g.inv_count[i]);
+}
+
 }  // namespace
 
 extern "C" int t2v_gn_bwd2(const void* x, int xc0, int ldx, const void* x1, int xc1, int ldx1, int n_units, int rows_per_unit,
@@ -668,6 +739,36 @@ extern "C" int t2v_attn_temporal_bwd(const void* q, int ldq, const void* k, int 
     hipLaunchKernelGGL(attn_temporal_bwd_kernel, dim3((unsigned)blocks), dim3(128), 0, (hipStream_t)stream, (const bf16_t*)q, ldq,
                        (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)dout, ldo, dprobs, (bf16_t*)dq, ldq2, (bf16_t*)dk, ldk2,
                        (bf16_t*)dv, ldv2, n_clips, frames, hw, heads, scale);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_rank_loss(const t2v_rank_loss_problem* p, int n_problems, int n, int rank_k, float alpha, float* ws,
+                             long long ws_floats, float* loss, void* stream) {
+    T2V_REQUIRE(p && ws && loss && n_problems >= 1 && n_problems <= T2V_RANK_LOSS_MAX, T2V_EINVAL, "t2v_rank_loss: 1..16 problems");
+    T2V_REQUIRE(n >= 1 && n <= 64 && rank_k >= 1 && rank_k <= n, T2V_ESHAPE, "t2v_rank_loss: 1 <= rank_k <= n <= 64");
+    int lg = 0;
+    while ((1 << lg) < n) ++lg;
+    const long long wg_rows = T2V_RANK_LOSS_WG_LANES >> lg;
+    RankLossGroup g;
+    long long blocks = 0;
+    for (int i = 0; i < n_problems; ++i) {
+        T2V_REQUIRE(p[i].ref && p[i].gen && p[i].d_gen && p[i].rows > 0, T2V_EINVAL, "t2v_rank_loss: bad problem");
+        g.p[i] = p[i];
+        const double count = (double)p[i].rows * (double)rank_k;
+        g.coef[i] = (float)((double)alpha * 2.0 / count);
+        g.inv_count[i] = 1.0 / count;
+        g.first_block[i] = (int)blocks;
+        blocks += (p[i].rows + wg_rows - 1) / wg_rows;
+        T2V_REQUIRE(blocks < (1ll << 31), T2V_ESHAPE, "t2v_rank_loss: too many rows");
+    }
+    for (int i = n_problems; i <= T2V_RANK_LOSS_MAX; ++i) g.first_block[i] = (int)blocks;
+    g.n_problems = n_problems;
+    T2V_REQUIRE(ws_floats >= blocks, T2V_ESHAPE, "t2v_rank_loss: workspace smaller than one float per workgroup");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rank_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, n, lg, rank_k, ws);
+    T2V_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rank_loss_final_kernel, dim3((unsigned)n_problems), dim3(256), 0, s, g, (const float*)ws, loss);
     T2V_CHECK_LAUNCH();
     return T2V_OK;
 }

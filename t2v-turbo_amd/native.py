@@ -29,6 +29,15 @@ class WgradProblem(C.Structure):
                 ("ldo", C.c_int), ("R", C.c_int), ("C", C.c_int), ("alpha", C.c_float)]
 
 
+RANK_LOSS_MAX = 16          # T2V_RANK_LOSS_MAX
+RANK_LOSS_WG_LANES = 2048   # T2V_RANK_LOSS_WG_LANES
+
+
+class RankLossProblem(C.Structure):
+    """struct t2v_rank_loss_problem, field for field."""
+    _fields_ = [("ref", C.c_void_p), ("gen", C.c_void_p), ("d_gen", C.c_void_p), ("rows", C.c_longlong)]
+
+
 ROWLIN_MAX_ROWS = 8       # T2V_ROWLIN_MAX_ROWS
 ROWLIN_LDS_FLOATS = 16384  # t2v_rowlin_fwd: B * K of a problem (its input rows wait in LDS)
 
@@ -258,6 +267,7 @@ _SIGS = {
     "t2v_wgrad_tn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "t2v_wgrad_tn_group": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "t2v_rank_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "t2v_gn_coef_cs_supported": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "t2v_gn_coef_cs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
@@ -949,6 +959,30 @@ class HipOps:
                 d.lda, d.ldb, d.ldo, d.R, d.C, d.alpha = _row_stride(a), _row_stride(b), _row_stride(out), a.shape[1], b.shape[1], alpha
             ws = self.workspace(chunk[0][0].device)
             self._call("t2v_wgrad_tn_group", C.cast(arr, C.c_void_p), len(chunk), ws.data_ptr(), ws.numel(), keep=arr)
+
+    # ---- the motion-prior loss on the recorded temporal attention probabilities (csrc/backward_unet.hip: t2v_rank_loss) ----------------
+    @staticmethod
+    def rank_loss_ws_floats(rows, n):
+        """Workspace of ``rank_loss`` for problems of ``rows`` = [rows_p] rows of ``n`` values: one float per workgroup."""
+        nh = 1
+        while nh < n:
+            nh *= 2
+        wg_rows = RANK_LOSS_WG_LANES // nh
+        return sum((r + wg_rows - 1) // wg_rows for r in rows)
+
+    def rank_loss(self, problems, n, rank_k, alpha, ws, loss):
+        """``problems``: [(ref, gen, d_gen)] contiguous fp32 tensors of rows x ``n`` values each, at most 16.  loss[p] = mean over the
+        top-``rank_k`` entries (by ``ref``) of every row of (gen - ref)^2; d_gen = ``alpha`` * d(loss[p]) / d(gen), every element written
+        (t2v_rank_loss: one launch pair for all problems, fixed-order sums)."""
+        arr = (RankLossProblem * len(problems))()
+        for d, (ref, gen, d_gen) in zip(arr, problems):
+            for t in (ref, gen, d_gen):
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ref.numel() and t.numel() % n == 0
+            d.ref, d.gen, d.d_gen, d.rows = _p(ref), _p(gen), _p(d_gen), ref.numel() // n
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and loss.dtype == torch.float32 and loss.is_contiguous()
+        assert loss.numel() >= len(problems)
+        self._call("t2v_rank_loss", C.cast(arr, C.c_void_p), len(problems), int(n), int(rank_k), float(alpha), _p(ws), ws.numel(), _p(loss),
+                   keep=arr)
 
     # ---- the B-row conditioning branch (csrc/full_grad.hip: t2v_rowlin_*) ----------------------------------------------------------
     # A problem is a dict of tensors and flags, the same for the three entries (see ``t2v_rowlin_problem``): x, w, bias, res, y (fwd: the

@@ -14,6 +14,7 @@ class EngineBox:
         self.enc = None
         self.grad = None
         self.full = None
+        self.input = None
 
     def __deepcopy__(self, memo):
         return EngineBox()

@@ -458,6 +458,33 @@ class _NativeStudentFull(torch.autograd.Function):
         return (dx.to(ctx.x_dtype), d_emb, None, None, *grads)
 
 
+class _NativeInputGrad(torch.autograd.Function):
+    """UNet forward of a FROZEN network whose backward — d/d(latents) of a loss on the output and / or on the recorded temporal
+    attention probabilities — runs on the data-gradient engine with nothing bound (motion_prior_sample.py:59-84:
+    ``unet(latents.requires_grad_(True), ...)``, ``attn1.attention_probs``, ``autograd.grad(loss, latents)``).  Outputs: the prediction
+    and one copy of every recorded probability tensor, in the engine's recording order (the route hangs them on the modules)."""
+
+    @staticmethod
+    def forward(ctx, x, model, args):
+        eng = model.native_input_engine()
+        y = eng.forward_tape(x.detach(), *args)
+        ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
+        ctx.attns = [attn for attn, _ in eng._last["probs"]]
+        ctx.x_dtype = x.dtype
+        ctx.set_materialize_grads(False)     # a loss on the probabilities alone leaves dout None, and the other way round
+        return (y, *[probs.clone() for _, probs in eng._last["probs"]])
+
+    @staticmethod
+    def backward(ctx, dout, *dprobs):
+        eng = ctx.model.native_input_engine()
+        if ctx.plan["fwd_id"] != ctx.fwd_id:
+            raise RuntimeError("native input gradient: another grad-mode forward of the same shape ran before this backward "
+                               "(the engine keeps one outstanding tape per input shape)")
+        eng._last = ctx.plan
+        dx = eng.backward(dout, {attn: g for attn, g in zip(ctx.attns, dprobs) if g is not None})
+        return dx.to(ctx.x_dtype), None, None
+
+
 class UNetModel(nn.Module):
     """Same constructor signature as the reference (openaimodel3d.py:340-374)."""
 
@@ -580,8 +607,13 @@ class UNetModel(nn.Module):
             if not any(is_lora_leaf(mod) for mod in walk_modules(self)) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                 return self._forward_native_full(x, timesteps, context, fps, timestep_cond, motion_cond)
             return self._forward_native_train(x, timesteps, context, fps, timestep_cond, motion_cond)
+        if mode == "input_grad" and torch.is_grad_enabled() and x.requires_grad:
+            # force the input-gradient route (raises where it cannot run); a call that asks for no gradient is answered as in "auto"
+            return self._forward_native_input(x, timesteps, context, fps, timestep_cond, motion_cond)
         if mode != "off" and x.is_cuda:  # "off": always the torch path
             route, why = self._auto_route(x, context, timestep_cond, features_adapter)
+            if route == "input_grad":
+                return self._forward_native_input(x, timesteps, context, fps, timestep_cond, motion_cond, routed=True)
             if route == "infer":
                 return self.native_engine()(x, timesteps, context, fps, timestep_cond, motion_cond)
             if route == "train":
@@ -602,8 +634,12 @@ class UNetModel(nn.Module):
           * no LoRA, gradients wanted and at least one parameter trainable — FULL fine-tuning, the student of
             train_latent_t2v_turbo_v2.py:669,798-816,1262 (train mode with the TemporalConvBlock dropouts live, or eval)
                                                              -> "train_full": gradient engine with base-weight gradients (engine_full.py);
-          * anything else (gradients w.r.t. the context, input gradients of a frozen network through this route, adapters, other live
-            dropouts)                                        -> the torch composite path, with a one-time warning."""
+          * no LoRA, NO parameter trainable, gradients wanted w.r.t. the latents only, no live dropout, and ``native_input_grad`` on —
+            the motion-prior score of motion_prior_sample.py:59-84 and preprocess_with_motion_prior.py:246,360 (frozen eval-mode
+            network, ``latents.requires_grad_(True)``, a loss on the recorded ``attention_probs`` and / or the output)
+                                                             -> "input_grad": data-gradient engine with nothing bound (opt-in);
+          * anything else (gradients w.r.t. the context, input gradients of a frozen network with ``native_input_grad`` off or left in
+            train mode, adapters, other live dropouts)       -> the torch composite path, with a one-time warning."""
         from .nn_util import walk_modules, walk_parameters
         grad = torch.is_grad_enabled() and self._needs_grad(x, context, timestep_cond)
         mods = walk_modules(self) if (self.training or grad) else ()
@@ -622,6 +658,11 @@ class UNetModel(nn.Module):
             return "infer", None
         lora_ids = {id(w) for mod in mods if is_lora_leaf(mod) for w in (mod.lora_up.weight, mod.lora_down.weight)}
         if not lora_ids:
+            if (grad and x.requires_grad and context is not None and self.input_grad_route_on()
+                    and not (context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad))
+                    and not any(p.requires_grad for p in walk_parameters(self))
+                    and not any(isinstance(mod, nn.Dropout) and mod.p > 0 and mod.training for mod in mods)):
+                return "input_grad", None
             if (grad and self.native_full and context is not None and any(p.requires_grad for p in walk_parameters(self))
                     and not (context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad))
                     and (not self.training or self._only_tconv_dropouts(mods))):
@@ -671,7 +712,7 @@ class UNetModel(nn.Module):
     @native_checkpoint.setter
     def native_checkpoint(self, on):
         self.__dict__["_native_checkpoint"] = None if on is None else bool(on)
-        for slot in ("full", "grad", "enc"):
+        for slot in ("full", "grad", "enc", "input"):
             eng = getattr(self._engine_box, slot, None)
             if eng is not None:
                 eng.checkpoint_blocks = self.native_checkpoint
@@ -720,6 +761,59 @@ class UNetModel(nn.Module):
         emb_all = None if eng.owns_conditioning(x.shape[0]) else self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
         args = (timesteps, context, fps, timestep_cond, motion_cond)
         return _NativeStudentFull.apply(x, emb_all, self, args, *eng.full_params)
+
+    # ---- input gradients of a frozen network through the module call (opt-in) --------------------------------------------------------
+    @property
+    def native_input_grad(self):
+        """None (default): follows T2V_NATIVE_INPUT_GRAD [0 | 1] (off when unset), read when a call is routed — the first call that takes
+        the route builds the engine; True / False: a CUDA call of this frozen module that wants d/d(latents) only lands on the
+        data-gradient engine (route "input_grad" of ``_auto_route``) / on the torch composite path as before."""
+        return self.__dict__.get("_native_input_grad")
+
+    @native_input_grad.setter
+    def native_input_grad(self, on):
+        self.__dict__["_native_input_grad"] = None if on is None else bool(on)
+
+    def input_grad_route_on(self):
+        """The switch as ``_auto_route`` reads it (``native_mode = "input_grad"`` forces the route and counts as on)."""
+        if getattr(self, "native_mode", "auto") == "input_grad":
+            return True
+        on = self.native_input_grad
+        return os.environ.get("T2V_NATIVE_INPUT_GRAD", "0") == "1" if on is None else on
+
+    def native_input_engine(self):
+        """The data-gradient engine with NOTHING bound: frozen packs, d/d(latents) only (engine_unet_bwd.py).  It refuses live dropouts
+        and checkpointing of blocks that record ``attention_probs``."""
+        if getattr(self._engine_box, "input", None) is None:
+            from .engine_unet_bwd import UNetGradEngine
+            make_ops = getattr(self, "_native_ops_factory", None)  # tests substitute the emulated backend
+            if make_ops is None:
+                from .native import HipOps as make_ops
+            eng = UNetGradEngine(self, make_ops())
+            eng.checkpoint_blocks = self.native_checkpoint
+            self._engine_box.input = eng
+        return self._engine_box.input
+
+    def _forward_native_input(self, x, timesteps, context, fps, timestep_cond, motion_cond, routed=False):
+        """``routed``: ``_auto_route`` sent the call here, its conditions hold; the forced mode checks them and raises."""
+        if not routed:
+            if not (x.is_cuda or getattr(self, "_native_ops_factory", None) is not None):
+                raise RuntimeError("the native input-gradient route needs CUDA tensors")
+            if context is None:
+                raise ValueError("the native input-gradient route needs the text context")
+            from .engine import is_lora_leaf
+            from .nn_util import walk_modules, walk_parameters
+            if any(is_lora_leaf(mod) for mod in walk_modules(self)) or any(p.requires_grad for p in walk_parameters(self)):
+                raise RuntimeError("the native input-gradient route takes a frozen network without LoRA injection "
+                                   "(trainable parameters go through the training routes)")
+            if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
+                raise RuntimeError("the native input-gradient route: gradients flow to the latents only")
+        eng = self.native_input_engine()
+        outs = _NativeInputGrad.apply(x, self, (timesteps, context, fps, timestep_cond, motion_cond))
+        # what the reference reads after the call (motion_prior_sample.py:40-57) is connected to the graph: the function's own outputs
+        for (attn, _), probs in zip(eng._last["probs"], outs[1:]):
+            attn.attention_probs = probs
+        return outs[0]
 
     # ---- native LoRA training (native_mode = "train") ---------------------------------------------------------------------
     def native_train_engine(self, forward_only=False):
