@@ -49,7 +49,7 @@ class FlatGradSync:
         off = 0
         for p in self.params:
             p.grad = self.flat[off:off + p.numel()].view_as(p)
-            p._t2v_flat_sync = self   # the native student writes its weight gradients straight into this buffer (unet3d._flat_grad_buffer)
+            p._t2v_flat_sync = self   # the native student writes its weight gradients straight into this buffer (bridge._flat_grad_buffer)
             off += p.numel()
         self.numel = n
         self.force = False        # True: the native engine exchanges its gradients even in a one-rank group (RCCL smoke tests)

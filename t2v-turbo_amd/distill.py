@@ -9,7 +9,7 @@ Execution split on MI355X: the two frozen-teacher forwards run on the native inf
 
 * default (``student_engine=None``) — the student is called as a module, ``unet(noisy, t, **context)`` and
   ``loss.backward()``, exactly as the reference trainer does; ``UNetModel.forward`` routes a LoRA-injected student whose only
-  trainable tensors are the LoRA ones to the gradient engine by itself (``unet3d._auto_route`` -> ``_NativeStudent``), in train
+  trainable tensors are the LoRA ones to the gradient engine by itself (``bridge.auto_route`` -> ``_NativeStudent``), in train
   mode (the reference's: LoRA / temporal-conv dropouts as counter-based masks) or eval mode.  Anything the engine cannot
   run (full fine-tuning, gradients w.r.t. the context) falls to the torch composite path with a one-time ``RuntimeWarning``;
 * ``student_engine=`` a ``UNetGradEngine`` with the LoRA tensors bound (``bind_lora``) — the same engine driven explicitly

@@ -436,12 +436,29 @@ class _Engine:
         self._replay(plan, "rec")
         return plan
 
-    @staticmethod
-    def _once_per_forward(plan, what):
-        """The backward consumes what its forward saved: one backward per forward."""
-        if plan.get("bwd_id") == plan["fwd_id"]:
+    # ---- tape protocol of the gradient engines: a plan keeps what ONE forward saved, and its backward consumes it --------
+    @property
+    def tape_token(self):
+        """(plan, fwd_id) of the most recent taped forward: what its backward hands to ``_claim_tape``."""
+        return self._last, self._last["fwd_id"]
+
+    def _end_tape(self, plan):
+        """A taped forward of ``plan`` is done: it is the one the next backward consumes."""
+        plan["fwd_id"] = plan.get("fwd_id", 0) + 1
+        self._last = plan
+        return self.tape_token
+
+    def _claim_tape(self, what, token=None):
+        """The plan a backward runs on: the one of ``token``, unless another forward went over its tape since (``_tape_refusal``);
+        the most recent forward's without a token.  The backward consumes what its forward saved: one backward per forward."""
+        plan, fwd_id = token or self.tape_token
+        if plan["fwd_id"] != fwd_id:
+            raise RuntimeError(self._tape_refusal)
+        if plan.get("bwd_id") == fwd_id:
             raise RuntimeError(f"{what}: backward was already run for this forward (its saved activations are gone)")
-        plan["bwd_id"] = plan["fwd_id"]
+        self._last = plan
+        plan["bwd_id"] = fwd_id
+        return plan
 
     @staticmethod
     def _capture(issue, device=None):

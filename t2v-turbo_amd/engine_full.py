@@ -12,7 +12,7 @@ The tape and the data gradients are the gradient engine's (engine_unet_bwd.py). 
   GroupNorm / LayerNorm    dgamma, dbeta                   ``t2v_norm_affine_grad`` kinds 0 / 1 (SiLU behind the norm included)
   time-embedding rows      d(loss)/d(emb_all)              per-clip column sums of the ResBlock's conv gradient (kind 2, sum_rows = F h w)
 
-into one fp32 tensor per parameter (``plan["fgrads"]``), which the autograd bridge (unet3d._NativeStudentFull) hands to torch.
+into one fp32 tensor per parameter (``plan["fgrads"]``), which the autograd bridge (bridge._NativeStudentFull) hands to torch.
 The conditioning branch (time / fps / guidance MLPs, ``emb_layers``: B rows) stays with torch autograd behind ``emb_all``, as in LoRA
 training — or, with ``native_conditioning`` on, runs on the engine as well (t2v_rowlin_* on the live fp32 parameters, no packs: nothing
 below that refreshes packs sees those leaves).  The weights change every optimizer step: the Packer re-fills its packs IN PLACE (``Packer.refresh``), so the recorded launch

@@ -33,6 +33,7 @@ import torch.nn as nn
 
 from . import native as nt
 from .native import on_tensor_device
+from .bridge import TriState
 from .engine import Act, Packer, UNetEngine, effective_weight_bias, is_lora_leaf, leaf_out_channels
 from .engine_full import FullTrainMixin
 from .engine_lora import LoraTrainMixin, _pad
@@ -56,23 +57,15 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
     # sets); ``UNetModel.native_checkpoint`` = True / False overrides the variable per module, and the attribute below can be set
     # on an engine at any time (a change of mode drops the recorded plans).
     _ckpt_env = os.environ.get("T2V_NATIVE_CHECKPOINT", "0")
-    _ckpt_set = None
 
-    @property
-    def checkpoint_blocks(self):
-        if self._ckpt_set is not None:
-            return self._ckpt_set
-        if self._ckpt_env == "model":
-            return bool(getattr(self.model, "use_checkpoint", False))
-        return self._ckpt_env == "1"
-
-    @checkpoint_blocks.setter
-    def checkpoint_blocks(self, on):
-        """True / False, or None: back to what T2V_NATIVE_CHECKPOINT says."""
-        before = self.checkpoint_blocks
-        self._ckpt_set = None if on is None else bool(on)
+    def _ckpt_changed(self, before):
         if self.checkpoint_blocks != before:
             self.plans.clear()                      # recorded launch lists are specific to the mode
+
+    checkpoint_blocks = TriState(
+        "True / False, or None: back to what T2V_NATIVE_CHECKPOINT says.",
+        follow=lambda self: bool(getattr(self.model, "use_checkpoint", False)) if self._ckpt_env == "model" else self._ckpt_env == "1",
+        changed=_ckpt_changed)
 
     # The B-row conditioning branch (time / fps / guidance MLPs, every ResBlock's emb_layers) on the engine instead of torch autograd:
     # recorded from the step's real inputs with the fp32 row kernels of csrc/full_grad.hip (t2v_rowlin_*), which read the master
@@ -80,21 +73,19 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
     # list.  Opt-in: T2V_NATIVE_COND=1 (read when the engine is built), ``UNetModel.native_conditioning`` = True / False per module,
     # or the attribute below on an engine (a change drops the recorded plans).  Full fine-tuning and LoRA training; a batch of more
     # than T2V_ROWLIN_MAX_ROWS clips (or input rows beyond the forward kernel's LDS) keeps the torch branch for that plan.
-    _cond_set = None
-
-    @property
-    def native_conditioning(self):
-        return self._cond_env if self._cond_set is None else self._cond_set
-
-    @native_conditioning.setter
-    def native_conditioning(self, on):
-        """True / False, or None: back to what T2V_NATIVE_COND said when the engine was built."""
-        before = self.native_conditioning
-        self._cond_set = None if on is None else bool(on)
+    def _cond_changed(self, before):
         if self.native_conditioning != before:
             self.plans.clear()
             if self.training_full:      # the conditioning leaves join / leave the parameters the engine differentiates
                 self.bind_full(self.engine_parameters(self.model, conditioning=self.native_conditioning))
+
+    native_conditioning = TriState("True / False, or None: back to what T2V_NATIVE_COND said when the engine was built.",
+                                   follow=lambda self: self._cond_env, changed=_cond_changed)
+
+    @property
+    def _tape_refusal(self):
+        return (f"{'native student' if self.trains else 'native input gradient'}: another grad-mode forward of the same shape ran "
+                "before this backward (the engine keeps one outstanding tape per input shape)")
 
     def owns_conditioning(self, batch):
         """The engine runs the conditioning branch of a training plan with ``batch`` clips itself (then ``forward_tape`` takes no emb_all)."""
@@ -178,13 +169,13 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             if "seed" in st:
                 self.seed_t = st["seed"]
             self._replay(plan, "rec")
-        plan["fwd_id"] = plan.get("fwd_id", 0) + 1
-        self._last = plan
+        self._end_tape(plan)
         self._publish_probs(plan)
         return plan["out"].clone()
 
-    def backward(self, dout=None, dprobs=None, flat_grad=None, accumulate=True, grad_sync=None):
-        """d(loss)/dx for the most recent ``forward_tape``.  ``dout``: gradient w.r.t. the output (or None = 0);
+    def backward(self, dout=None, dprobs=None, flat_grad=None, accumulate=True, grad_sync=None, token=None):
+        """d(loss)/dx for the ``forward_tape`` of ``token`` (``tape_token`` right after it; default: the most recent one).
+        ``dout``: gradient w.r.t. the output (or None = 0);
         ``dprobs``: {attention module: gradient w.r.t. its ``attention_probs``} for any of the recorded layers.
         LoRA training: the weight gradients land in ``flat_grad`` (fp32, ``bind_lora`` order; added to what is there
         when ``accumulate``) and ``self.d_emb_all`` holds d(loss)/d(emb_all) for the caller's torch branch.
@@ -193,11 +184,11 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
         hands over already averaged gradients; ``grad_sync.all_reduce_mean()`` afterwards only exchanges the conditioning
         branch's tensors.  T2V_ASYNC_ALLREDUCE=0 keeps the single blocking all-reduce after the backward.  Under ``use_graph``
         the backward list is captured as one hipGraph per run of launches between two markers."""
-        plan = self._last
+        plan = (token or self.tape_token)[0]
         if plan["out"].is_cuda and plan["out"].device.index != torch.cuda.current_device():
             with torch.cuda.device(plan["out"].device):
-                return self.backward(dout, dprobs, flat_grad, accumulate, grad_sync)
-        self._once_per_forward(plan, "UNet gradient")
+                return self.backward(dout, dprobs, flat_grad, accumulate, grad_sync, token)
+        self._claim_tape("UNet gradient", token)
         if self.training_full:
             self.full_activate(plan)              # (another signature's forward may have run since this plan's)
         st = plan["static"]
@@ -261,28 +252,21 @@ class UNetGradEngine(FullTrainMixin, LoraTrainMixin, UNetEngine):
             self.pk = Packer(self.adt, x.device, merge_lora=False)
             self._cond_owned = emb_all is None      # (the conditioning leaves' gradient slots are part of the arena then)
             self._lora_begin()
-            if emb_all is not None:
-                st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
-                plan["d_emb"] = torch.zeros_like(st["emb_all"])
-            else:
-                plan["d_emb"] = torch.zeros(B, self._emb_table()[1], dtype=torch.float32, device=x.device)
-                plan["cond_ptrs"] = self._cond_ptrs()
-            st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
-            self.seed_t = st["seed"]
         if self.training_full:
             # plain leaves on packs of the current weights (re-filled in place per step: Packer.refresh); one fp32 gradient per parameter
             self.pk = Packer(self.adt, x.device)
+            plan["fgrads"] = {}
+            from .engine import params_fingerprint
+            plan["full_fp"] = params_fingerprint(m)   # the weights this plan's packs are made from, while it is recorded
+        if self.trains:
             if emb_all is not None:
                 st["emb_all"] = emb_all.detach().to(x.device, torch.float32).clone().contiguous()
                 plan["d_emb"] = torch.zeros_like(st["emb_all"])
             else:   # the engine owns the conditioning branch: emb_all is made by the recorded forward, d_emb consumed by the recorded backward
                 plan["d_emb"] = torch.zeros(B, self._emb_table()[1], dtype=torch.float32, device=x.device)
                 plan["cond_ptrs"] = self._cond_ptrs()
-            plan["fgrads"] = {}
             st["seed"] = torch.full((1,), getattr(self, "_seed", 0), dtype=torch.int64, device=x.device)
             self.seed_t = st["seed"]
-            from .engine import params_fingerprint
-            plan["full_fp"] = params_fingerprint(m)   # the weights this plan's packs are made from, while it is recorded
         plan["geom"] = (B, F)
         self.plan = plan
         self.tape, self.refs = [], {}

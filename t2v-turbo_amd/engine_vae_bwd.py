@@ -22,6 +22,9 @@ from .vae import AttnBlock
 
 
 class VAEDecodeGradEngine(VAEDecodeEngine):
+    _tape_refusal = ("native VAE decode gradient keeps ONE outstanding decode per input shape: another decode of "
+                     "the same shape ran before this backward (set vae.native_mode = 'off' for the torch path)")
+
     def __init__(self, vae, ops):
         super().__init__(vae, ops)
         self.use_graph = False   # T2V_HIP_GRAPH=1 does not apply here: hipGraph capture of this engine's two lists is not validated
@@ -33,15 +36,13 @@ class VAEDecodeGradEngine(VAEDecodeEngine):
         self._check_weights(self.vae)
         key = ("grad", tuple(z.shape), z.dtype, float(scale), z.device)
         plan = self._lookup_or_record(key, lambda: self._record_grad(z, scale), lambda st: st["z"].copy_(z))
-        plan["fwd_id"] = plan.get("fwd_id", 0) + 1
-        self._last = plan
+        self._end_tape(plan)
         return plan["out"].clone()
 
     @on_tensor_device
-    def backward(self, dout):
-        """d(loss)/dz for the most recent ``decode_frames_tape`` call."""
-        plan = self._last
-        self._once_per_forward(plan, "VAE decode gradient")
+    def backward(self, dout, token=None):
+        """d(loss)/dz for the ``decode_frames_tape`` call of ``token`` (``tape_token`` right after it; default: the most recent call)."""
+        plan = self._claim_tape("VAE decode gradient", token)
         plan["static"]["dout"].copy_(dout)
         self._replay(plan, "rec_bwd")
         return plan["dz"].clone()

@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .nn_util import EngineBox, sinusoidal_embedding
+from .bridge import EngineBox, needs_grad
+from .nn_util import sinusoidal_embedding
 from .unet3d import SpatialTransformer, TemporalConvBlock, TemporalTransformer
 
 
@@ -347,8 +348,8 @@ class UNet3DConditionModel(nn.Module):
             timesteps = timesteps[None].to(sample.device)
         timesteps = timesteps.expand(sample.shape[0])
         native = getattr(self, "native_mode", "auto") != "off"
-        if native and sample.is_cuda and sample.shape[2] > 1 and not (torch.is_grad_enabled() and self._needs_grad(
-                sample, encoder_hidden_states, timestep_cond)):
+        if native and sample.is_cuda and sample.shape[2] > 1 and not (torch.is_grad_enabled() and needs_grad(
+                self, sample, encoder_hidden_states, timestep_cond)):
             if any(s % (2 ** self.num_upsamplers) for s in sample.shape[-2:]):
                 raise NotImplementedError("native ModelScope path needs H, W divisible by 2**num_upsamplers")
             out = self.native_engine()(sample, timesteps.contiguous(), encoder_hidden_states, 16, timestep_cond, None)
@@ -356,17 +357,8 @@ class UNet3DConditionModel(nn.Module):
             out = self._forward_composite(sample, timesteps, encoder_hidden_states, timestep_cond)
         return UNet3DConditionOutput(out) if return_dict else (out,)
 
-    def _needs_grad(self, *tensors):
-        if any(t is not None and t.requires_grad for t in tensors):
-            return True
-        return any(p.requires_grad for p in self.parameters())
-
     def native_engine(self):
-        if self._engine_box.engine is None:
-            from .engine_ms import MSUNetEngine
-            from .native import HipOps
-            self._engine_box.engine = MSUNetEngine(self, HipOps())
-        return self._engine_box.engine
+        return self._engine_box.get("engine", "engine_ms.MSUNetEngine", self)
 
     def _forward_composite(self, sample, timesteps, ctx, timestep_cond):
         """Reference-semantics torch path (unet_3d_condition.py:360-503)."""

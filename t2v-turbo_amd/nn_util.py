@@ -4,23 +4,7 @@ import math
 import torch
 import torch.utils.checkpoint
 
-
-class EngineBox:
-    """Holds a lazily built native engine next to an nn.Module without making it part of the module:
-    copies / pickles of the module start with an empty box (engines own device buffers)."""
-
-    def __init__(self):
-        self.engine = None
-        self.enc = None
-        self.grad = None
-        self.full = None
-        self.input = None
-
-    def __deepcopy__(self, memo):
-        return EngineBox()
-
-    def __reduce__(self):
-        return (EngineBox, ())
+from .bridge import EngineBox  # noqa: F401  (re-exported)
 
 
 def checkpoint_call(fn, inputs, flag):
@@ -71,10 +55,11 @@ def walk_modules(root):
     return out
 
 
-def walk_parameters(root):
-    """Every distinct parameter under ``root`` in a fixed (not ``parameters()``'s) order, without building names."""
+def walk_parameters(root, mods=None):
+    """Every distinct parameter under ``root`` in a fixed (not ``parameters()``'s) order, without building names.  ``mods``: the
+    ``walk_modules(root)`` the caller already has."""
     out, seen = [], set()
-    for mod in walk_modules(root):
+    for mod in mods or walk_modules(root):
         for p in mod._parameters.values():
             if p is not None and id(p) not in seen:
                 seen.add(id(p))

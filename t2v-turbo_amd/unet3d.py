@@ -20,7 +20,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .nn_util import EngineBox, checkpoint_call, sinusoidal_embedding
+from . import bridge
+from .bridge import _WARNED_ATEN, _warn_aten_route  # noqa: F401  (kept importable from here)
+from .nn_util import checkpoint_call, sinusoidal_embedding
 
 
 class GroupNormSpecific(nn.GroupNorm):
@@ -354,137 +356,6 @@ class ResBlock(TimestepBlock):
 
 
 # =================================================================================== the UNet
-_WARNED_ATEN = set()
-
-
-def _warn_aten_route(why):
-    """The torch composite path on a CUDA tensor is a fallback (ATen kernels, ~3x slower than the native engines): say so once
-    per reason."""
-    if why not in _WARNED_ATEN:
-        _WARNED_ATEN.add(why)
-        import warnings
-        warnings.warn(f"t2v_turbo_amd UNetModel: running the torch (ATen) path on a CUDA tensor — {why}; "
-                      'set native_mode = "off" to silence, see INTEGRATION.md', RuntimeWarning, stacklevel=3)
-
-
-def _flat_grad_buffer(eng, leaves):
-    """The ``dist.FlatGradSync`` whose flat fp32 buffer's slots ARE the LoRA tensors' ``.grad`` (same order and
-    offsets as ``bind_lora``), or None.  Only a buffer that announced itself (``FlatGradSync`` tags its parameters) is taken:
-    writing into ``.grad`` bypasses AccumulateGrad, so a look-alike layout owned by somebody else — DDP's
-    ``gradient_as_bucket_view`` bucket, accelerate's reducer — or any parameter with gradient hooks gets its gradients
-    through autograd instead (the hooks then fire as usual)."""
-    sync = getattr(eng.lora_params[0], "_t2v_flat_sync", None)
-    if sync is None or sync.flat.dtype != torch.float32 or sync.numel != eng.lora_numel:
-        return None
-    base = sync.flat.data_ptr()
-    for p in eng.lora_params:
-        g = p.grad
-        if getattr(p, "_t2v_flat_sync", None) is not sync or g is None or g.dtype != torch.float32 or not g.is_contiguous() \
-                or g.data_ptr() != base + 4 * eng.lora_off[id(p)]:
-            return None
-        if p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-            return None
-    return sync
-
-
-class _NativeStudent(torch.autograd.Function):
-    """UNet forward whose backward — d/d(latents), d/d(emb_all) and every token-row LoRA weight gradient — runs on the native
-    gradient engine.  Inputs: latents, the conditioning branch's output (torch keeps differentiating behind it), and the
-    LoRA tensors the engine owns (so autograd routes their gradients to the optimizer's ``.grad`` slots)."""
-
-    @staticmethod
-    def forward(ctx, x, emb_all, model, args, *leaves):
-        eng = model.native_train_engine()
-        timesteps, context, fps, tc, mc = args
-        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=None if emb_all is None else emb_all.detach())
-        ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
-        ctx.leaves = leaves
-        ctx.x_dtype, ctx.e_dtype = x.dtype, None if emb_all is None else emb_all.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dout):
-        eng = ctx.model.native_train_engine()
-        if ctx.plan["fwd_id"] != ctx.fwd_id:
-            raise RuntimeError("native student: another grad-mode forward of the same shape ran before this backward "
-                               "(the engine keeps one outstanding tape per input shape)")
-        eng._last = ctx.plan
-
-        def d_emb():    # (emb_all is None when the engine owns the conditioning branch: its LoRA tensors are among ``leaves`` then)
-            return None if ctx.e_dtype is None else eng.d_emb_all.to(ctx.e_dtype).clone()
-        sync = _flat_grad_buffer(eng, ctx.leaves)
-        if sync is not None:
-            # every LoRA tensor's .grad is already its slot of ONE flat fp32 buffer in bind_lora order (dist.FlatGradSync): the engine
-            # adds its weight gradients there in one launch — what 1096 AccumulateGrad nodes would do with 1096 small kernels
-            dx = eng.backward(dout, flat_grad=sync.flat, accumulate=True, grad_sync=sync)
-            return (dx.to(ctx.x_dtype), d_emb(), None, None, *([None] * len(ctx.leaves)))
-        flat = torch.empty(eng.lora_numel, dtype=torch.float32, device=dout.device)  # fresh: .grad may keep views of it
-        dx = eng.backward(dout, flat_grad=flat, accumulate=False)
-        grads = []
-        for p in ctx.leaves:
-            o = eng.lora_off[id(p)]
-            grads.append(flat[o:o + p.numel()].view_as(p).to(p.dtype))
-        return (dx.to(ctx.x_dtype), d_emb(), None, None, *grads)
-
-
-class _NativeStudentFull(torch.autograd.Function):
-    """UNet forward of the FULL fine-tuning student (train_latent_t2v_turbo_v2.py:669,798-816,1262: every parameter trainable, no LoRA):
-    d/d(latents), d/d(emb_all) and the gradient of every parameter outside the B-row conditioning branch come from the native gradient
-    engine (engine_full.py); torch keeps differentiating the conditioning branch behind ``emb_all``.  With ``native_conditioning`` on
-    the engine owns that branch too: ``emb_all`` is None, the conditioning parameters are among ``params``, and the autograd graph
-    behind the output is this node and the parameters' AccumulateGrad nodes."""
-
-    @staticmethod
-    def forward(ctx, x, emb_all, model, args, *params):
-        eng = model.native_full_engine()
-        timesteps, context, fps, tc, mc = args
-        y = eng.forward_tape(x.detach(), timesteps, context.detach(), fps, tc, mc, emb_all=None if emb_all is None else emb_all.detach())
-        ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
-        ctx.params = params
-        ctx.x_dtype, ctx.e_dtype = x.dtype, None if emb_all is None else emb_all.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dout):
-        eng = ctx.model.native_full_engine()
-        if ctx.plan["fwd_id"] != ctx.fwd_id:
-            raise RuntimeError("native student: another grad-mode forward of the same shape ran before this backward "
-                               "(the engine keeps one outstanding tape per input shape)")
-        eng._last = ctx.plan
-        dx = eng.backward(dout)
-        grads = [None if (g is None or not p.requires_grad) else g.to(p.dtype) for p, g in zip(ctx.params, eng.full_grads(ctx.params))]
-        # (emb_all is None when the engine owns the conditioning branch: its parameters are among ``params`` then)
-        d_emb = None if ctx.e_dtype is None else eng.d_emb_all.to(ctx.e_dtype).clone()
-        return (dx.to(ctx.x_dtype), d_emb, None, None, *grads)
-
-
-class _NativeInputGrad(torch.autograd.Function):
-    """UNet forward of a FROZEN network whose backward — d/d(latents) of a loss on the output and / or on the recorded temporal
-    attention probabilities — runs on the data-gradient engine with nothing bound (motion_prior_sample.py:59-84:
-    ``unet(latents.requires_grad_(True), ...)``, ``attn1.attention_probs``, ``autograd.grad(loss, latents)``).  Outputs: the prediction
-    and one copy of every recorded probability tensor, in the engine's recording order (the route hangs them on the modules)."""
-
-    @staticmethod
-    def forward(ctx, x, model, args):
-        eng = model.native_input_engine()
-        y = eng.forward_tape(x.detach(), *args)
-        ctx.model, ctx.plan, ctx.fwd_id = model, eng._last, eng._last["fwd_id"]
-        ctx.attns = [attn for attn, _ in eng._last["probs"]]
-        ctx.x_dtype = x.dtype
-        ctx.set_materialize_grads(False)     # a loss on the probabilities alone leaves dout None, and the other way round
-        return (y, *[probs.clone() for _, probs in eng._last["probs"]])
-
-    @staticmethod
-    def backward(ctx, dout, *dprobs):
-        eng = ctx.model.native_input_engine()
-        if ctx.plan["fwd_id"] != ctx.fwd_id:
-            raise RuntimeError("native input gradient: another grad-mode forward of the same shape ran before this backward "
-                               "(the engine keeps one outstanding tape per input shape)")
-        eng._last = ctx.plan
-        dx = eng.backward(dout, {attn: g for attn, g in zip(ctx.attns, dprobs) if g is not None})
-        return dx.to(ctx.x_dtype), None, None
-
-
 class UNetModel(nn.Module):
     """Same constructor signature as the reference (openaimodel3d.py:340-374)."""
 
@@ -593,186 +464,56 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(nn.Conv2d(mc, out_channels, 3, padding=1)))
-        self._engine_box = EngineBox()
+        self._engine_box = bridge.EngineBox()
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x, timesteps, context=None, features_adapter=None, fps=16, timestep_cond=None,
                 motion_cond=None, **kwargs):
         if motion_cond is not None:
             assert timestep_cond is not None
-        mode = getattr(self, "native_mode", "auto")
-        if mode == "train":  # force the native gradient engine (raises where it cannot run)
-            from .nn_util import walk_modules
-            from .engine import is_lora_leaf
-            if not any(is_lora_leaf(mod) for mod in walk_modules(self)) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                return self._forward_native_full(x, timesteps, context, fps, timestep_cond, motion_cond)
-            return self._forward_native_train(x, timesteps, context, fps, timestep_cond, motion_cond)
-        if mode == "input_grad" and torch.is_grad_enabled() and x.requires_grad:
-            # force the input-gradient route (raises where it cannot run); a call that asks for no gradient is answered as in "auto"
-            return self._forward_native_input(x, timesteps, context, fps, timestep_cond, motion_cond)
-        if mode != "off" and x.is_cuda:  # "off": always the torch path
-            route, why = self._auto_route(x, context, timestep_cond, features_adapter)
-            if route == "input_grad":
-                return self._forward_native_input(x, timesteps, context, fps, timestep_cond, motion_cond, routed=True)
-            if route == "infer":
-                return self.native_engine()(x, timesteps, context, fps, timestep_cond, motion_cond)
-            if route == "train":
-                return self._forward_native_train(x, timesteps, context, fps, timestep_cond, motion_cond)
-            if route == "train_full":
-                return self._forward_native_full(x, timesteps, context, fps, timestep_cond, motion_cond)
-            _warn_aten_route(why)
-        return self._forward_composite(x, timesteps, context, features_adapter, fps, timestep_cond, motion_cond)
+        return bridge.forward(self, x, timesteps, context, features_adapter, fps, timestep_cond, motion_cond)
 
     def _auto_route(self, x, context, timestep_cond, features_adapter):
-        """Which engine a CUDA call lands on (``native_mode = "auto"``):
-          * no gradient wanted, no active dropout            -> "infer": inference engine (LoRA branches merged at pack time);
-          * LoRA-injected student, only LoRA tensors trainable, with or without grad, train or eval mode
-            (the student and target forwards of train_t2v_turbo_v1_lora.py:1022-1028,1161-1168)
-                                                             -> "train": gradient engine (un-merged LoRA branch, counter-based dropout);
-          * no gradient wanted, no LoRA, train mode with only the TemporalConvBlock dropouts live (the v1 teacher, which the
-            reference never puts in eval mode)               -> "infer": inference engine + counter-based dropout masks;
-          * no LoRA, gradients wanted and at least one parameter trainable — FULL fine-tuning, the student of
-            train_latent_t2v_turbo_v2.py:669,798-816,1262 (train mode with the TemporalConvBlock dropouts live, or eval)
-                                                             -> "train_full": gradient engine with base-weight gradients (engine_full.py);
-          * no LoRA, NO parameter trainable, gradients wanted w.r.t. the latents only, no live dropout, and ``native_input_grad`` on —
-            the motion-prior score of motion_prior_sample.py:59-84 and preprocess_with_motion_prior.py:246,360 (frozen eval-mode
-            network, ``latents.requires_grad_(True)``, a loss on the recorded ``attention_probs`` and / or the output)
-                                                             -> "input_grad": data-gradient engine with nothing bound (opt-in);
-          * anything else (gradients w.r.t. the context, input gradients of a frozen network with ``native_input_grad`` off or left in
-            train mode, adapters, other live dropouts)       -> the torch composite path, with a one-time warning."""
-        from .nn_util import walk_modules, walk_parameters
-        grad = torch.is_grad_enabled() and self._needs_grad(x, context, timestep_cond)
-        mods = walk_modules(self) if (self.training or grad) else ()
-        dropping = self.training and any(isinstance(mod, nn.Dropout) and mod.p > 0 for mod in mods)
-        if features_adapter is not None:
-            if not grad and not dropping:
-                raise NotImplementedError("features_adapter is not used by t2v-turbo and not supported natively")
-            return "composite", "features_adapter"
-        if not grad and not dropping:
-            return "infer", None
-        from .engine import is_lora_leaf
-        if not grad and not any(is_lora_leaf(mod) for mod in mods) and self._only_tconv_dropouts(mods):
-            # a frozen, LoRA-free network left in train mode under no_grad: the v1 distillation teacher as the reference runs it
-            # (train_t2v_turbo_v1_lora.py:621-626 never calls .eval(); forwards at :1105-1134) — inference dataflow + the
-            # TemporalConvBlock dropouts as counter-based masks
-            return "infer", None
-        lora_ids = {id(w) for mod in mods if is_lora_leaf(mod) for w in (mod.lora_up.weight, mod.lora_down.weight)}
-        if not lora_ids:
-            if (grad and x.requires_grad and context is not None and self.input_grad_route_on()
-                    and not (context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad))
-                    and not any(p.requires_grad for p in walk_parameters(self))
-                    and not any(isinstance(mod, nn.Dropout) and mod.p > 0 and mod.training for mod in mods)):
-                return "input_grad", None
-            if (grad and self.native_full and context is not None and any(p.requires_grad for p in walk_parameters(self))
-                    and not (context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad))
-                    and (not self.training or self._only_tconv_dropouts(mods))):
-                return "train_full", None
-            return "composite", ("a train-mode network with active Dropout and no LoRA" if not grad else
-                                 "gradients without LoRA injection that the native full fine-tuning route does not take (input gradients only, "
-                                 "gradients w.r.t. the context, other live dropouts, T2V_NATIVE_FULL=0)")
-        if context is None:
-            return "composite", "no text context"
-        if any(p.requires_grad and id(p) not in lora_ids for p in walk_parameters(self)):
-            return "composite", "trainable parameters besides the LoRA tensors"
-        if grad and (context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad)):
-            return "composite", "gradients w.r.t. the context / guidance embedding"
-        return "train", None
+        """Which engine a CUDA call lands on under ``native_mode = "auto"``: (route, reason when it is "composite") — ``bridge.auto_route``."""
+        return bridge.auto_route(bridge.Call(self, x, context, timestep_cond, features_adapter))
 
-    @staticmethod
-    def _only_tconv_dropouts(mods):
-        """Every active Dropout(p > 0) sits in a TemporalConvBlock stage (the only ones the inference engine applies)."""
-        known = set()
-        for blk in mods:
-            if isinstance(blk, TemporalConvBlock):
-                for stg in (blk.conv1, blk.conv2, blk.conv3, blk.conv4):
-                    known.update(id(layer) for layer in stg if isinstance(layer, nn.Dropout))
-        return all(id(mod) in known for mod in mods if isinstance(mod, nn.Dropout) and mod.p > 0 and mod.training)
-
-    def _needs_grad(self, *tensors):
-        if any(t is not None and t.requires_grad for t in tensors):
-            return True
-        return any(p.requires_grad for p in self.parameters())
-
+    # ---- the native engines next to this module (bridge.ROUTES: slots, switches, binding) ---------------------------------------
     def native_engine(self):
-        if self._engine_box.engine is None:
-            from .engine import UNetEngine
-            from .native import HipOps
-            self._engine_box.engine = UNetEngine(self, HipOps())
-        return self._engine_box.engine
-
-    # ---- activation checkpointing on the native training engines (UNetGradEngine.checkpoint_blocks) --------------------------------
-    @property
-    def native_checkpoint(self):
-        """None (default): the gradient engines follow T2V_NATIVE_CHECKPOINT [0 | 1 | model]; True / False: checkpointing on / off for the
-        engines of this module — every residual block and spatial / temporal transformer keeps only its input and is recomputed inside the
-        backward (the reference's ``use_checkpoint``).  Applied when an engine is built; setting it later goes through the engines'
-        ``checkpoint_blocks`` setter, which drops their recorded plans when the mode changes."""
-        return self.__dict__.get("_native_checkpoint")
-
-    @native_checkpoint.setter
-    def native_checkpoint(self, on):
-        self.__dict__["_native_checkpoint"] = None if on is None else bool(on)
-        for slot in ("full", "grad", "enc", "input"):
-            eng = getattr(self._engine_box, slot, None)
-            if eng is not None:
-                eng.checkpoint_blocks = self.native_checkpoint
-
-    # ---- the B-row conditioning branch on the native training engines (UNetGradEngine.native_conditioning) -------------------------
-    @property
-    def native_conditioning(self):
-        """None (default): the gradient engines follow T2V_NATIVE_COND [0 | 1], read when an engine is built; True / False: the time / fps /
-        guidance MLPs and every ResBlock's ``emb_layers`` run on the engine (fp32 row kernels on the live parameters, their gradients with
-        every other parameter's, or the LoRA tensors' in the flat arena) / stay with torch autograd behind ``emb_all``, for the engines of
-        this module: full fine-tuning and LoRA training.  Setting it later goes through the engines' setter, which drops their recorded plans."""
-        return self.__dict__.get("_native_conditioning")
-
-    @native_conditioning.setter
-    def native_conditioning(self, on):
-        self.__dict__["_native_conditioning"] = None if on is None else bool(on)
-        for slot in ("full", "grad", "enc"):
-            eng = getattr(self._engine_box, slot, None)
-            if eng is not None:
-                eng.native_conditioning = self.native_conditioning
-
-    # ---- native FULL fine-tuning (every parameter trainable, no LoRA: train_latent_t2v_turbo_v2.py) ---------------------------------
-    native_full = os.environ.get("T2V_NATIVE_FULL", "1") == "1"
+        return bridge.engine(self, "infer")
 
     def native_full_engine(self):
-        if getattr(self._engine_box, "full", None) is None:
-            from .engine_unet_bwd import UNetGradEngine
-            make_ops = getattr(self, "_native_ops_factory", None)  # tests substitute the emulated backend
-            if make_ops is None:
-                from .native import HipOps as make_ops
-            eng = UNetGradEngine(self, make_ops())
-            eng.checkpoint_blocks = self.native_checkpoint
-            eng.native_conditioning = self.native_conditioning
-            eng.bind_full(eng.engine_parameters(self, conditioning=eng.native_conditioning))
-            self._engine_box.full = eng
-        return self._engine_box.full
+        return bridge.engine(self, "train_full")
 
-    def _forward_native_full(self, x, timesteps, context, fps, timestep_cond, motion_cond):
-        if not (x.is_cuda or getattr(self, "_native_ops_factory", None) is not None):
-            raise RuntimeError("native full fine-tuning needs CUDA tensors")
-        if context is None:
-            raise ValueError("native full fine-tuning needs the text context")
-        if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
-            raise RuntimeError("native full fine-tuning: gradients flow to the latents and the parameters only")
-        eng = self.native_full_engine()
-        emb_all = None if eng.owns_conditioning(x.shape[0]) else self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
-        args = (timesteps, context, fps, timestep_cond, motion_cond)
-        return _NativeStudentFull.apply(x, emb_all, self, args, *eng.full_params)
+    def native_input_engine(self):
+        """The data-gradient engine with NOTHING bound: frozen packs, d/d(latents) only (engine_unet_bwd.py).  It refuses live dropouts
+        and checkpointing of blocks that record ``attention_probs``."""
+        return bridge.engine(self, "input_grad")
 
-    # ---- input gradients of a frozen network through the module call (opt-in) --------------------------------------------------------
-    @property
-    def native_input_grad(self):
-        """None (default): follows T2V_NATIVE_INPUT_GRAD [0 | 1] (off when unset), read when a call is routed — the first call that takes
-        the route builds the engine; True / False: a CUDA call of this frozen module that wants d/d(latents) only lands on the
-        data-gradient engine (route "input_grad" of ``_auto_route``) / on the torch composite path as before."""
-        return self.__dict__.get("_native_input_grad")
+    def native_train_engine(self, forward_only=False):
+        """Gradient engine with the LoRA tensors bound (engine_lora.py); ``forward_only``: the second instance, for no-grad forwards
+        between a forward and its backward."""
+        return bridge.engine(self, "train", "enc" if forward_only else "grad")
 
-    @native_input_grad.setter
-    def native_input_grad(self, on):
-        self.__dict__["_native_input_grad"] = None if on is None else bool(on)
+    native_checkpoint = bridge.TriState(
+        """Activation checkpointing on the native training engines (UNetGradEngine.checkpoint_blocks).  None (default): the gradient
+        engines follow T2V_NATIVE_CHECKPOINT [0 | 1 | model]; True / False: checkpointing on / off for the engines of this module — every
+        residual block and spatial / temporal transformer keeps only its input and is recomputed inside the backward (the reference's
+        ``use_checkpoint``).  Applied when an engine is built; setting it later goes through the engines' ``checkpoint_blocks`` setter,
+        which drops their recorded plans when the mode changes.""", changed=bridge.push_switch("native_checkpoint"))
+    native_conditioning = bridge.TriState(
+        """The B-row conditioning branch on the native training engines (UNetGradEngine.native_conditioning).  None (default): the
+        gradient engines follow T2V_NATIVE_COND [0 | 1], read when an engine is built; True / False: the time / fps / guidance MLPs and
+        every ResBlock's ``emb_layers`` run on the engine (fp32 row kernels on the live parameters, their gradients with every other
+        parameter's, or the LoRA tensors' in the flat arena) / stay with torch autograd behind ``emb_all``, for the engines of this
+        module: full fine-tuning and LoRA training.  Setting it later goes through the engines' setter, which drops their recorded
+        plans.""", changed=bridge.push_switch("native_conditioning"))
+    native_input_grad = bridge.TriState(
+        """Input gradients of a frozen network through the module call (opt-in).  None (default): follows T2V_NATIVE_INPUT_GRAD [0 | 1]
+        (off when unset), read when a call is routed — the first call that takes the route builds the engine; True / False: a CUDA call
+        of this frozen module that wants d/d(latents) only lands on the data-gradient engine (route "input_grad" of ``_auto_route``) /
+        on the torch composite path as before.""")
+    # native FULL fine-tuning (every parameter trainable, no LoRA: train_latent_t2v_turbo_v2.py)
+    native_full = os.environ.get("T2V_NATIVE_FULL", "1") == "1"
 
     def input_grad_route_on(self):
         """The switch as ``_auto_route`` reads it (``native_mode = "input_grad"`` forces the route and counts as on)."""
@@ -780,80 +521,6 @@ class UNetModel(nn.Module):
             return True
         on = self.native_input_grad
         return os.environ.get("T2V_NATIVE_INPUT_GRAD", "0") == "1" if on is None else on
-
-    def native_input_engine(self):
-        """The data-gradient engine with NOTHING bound: frozen packs, d/d(latents) only (engine_unet_bwd.py).  It refuses live dropouts
-        and checkpointing of blocks that record ``attention_probs``."""
-        if getattr(self._engine_box, "input", None) is None:
-            from .engine_unet_bwd import UNetGradEngine
-            make_ops = getattr(self, "_native_ops_factory", None)  # tests substitute the emulated backend
-            if make_ops is None:
-                from .native import HipOps as make_ops
-            eng = UNetGradEngine(self, make_ops())
-            eng.checkpoint_blocks = self.native_checkpoint
-            self._engine_box.input = eng
-        return self._engine_box.input
-
-    def _forward_native_input(self, x, timesteps, context, fps, timestep_cond, motion_cond, routed=False):
-        """``routed``: ``_auto_route`` sent the call here, its conditions hold; the forced mode checks them and raises."""
-        if not routed:
-            if not (x.is_cuda or getattr(self, "_native_ops_factory", None) is not None):
-                raise RuntimeError("the native input-gradient route needs CUDA tensors")
-            if context is None:
-                raise ValueError("the native input-gradient route needs the text context")
-            from .engine import is_lora_leaf
-            from .nn_util import walk_modules, walk_parameters
-            if any(is_lora_leaf(mod) for mod in walk_modules(self)) or any(p.requires_grad for p in walk_parameters(self)):
-                raise RuntimeError("the native input-gradient route takes a frozen network without LoRA injection "
-                                   "(trainable parameters go through the training routes)")
-            if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
-                raise RuntimeError("the native input-gradient route: gradients flow to the latents only")
-        eng = self.native_input_engine()
-        outs = _NativeInputGrad.apply(x, self, (timesteps, context, fps, timestep_cond, motion_cond))
-        # what the reference reads after the call (motion_prior_sample.py:40-57) is connected to the graph: the function's own outputs
-        for (attn, _), probs in zip(eng._last["probs"], outs[1:]):
-            attn.attention_probs = probs
-        return outs[0]
-
-    # ---- native LoRA training (native_mode = "train") ---------------------------------------------------------------------
-    def native_train_engine(self, forward_only=False):
-        """Gradient engine with the LoRA tensors bound (engine_lora.py).  Two instances: one whose tape the backward consumes,
-        one for no-grad forwards in between (the distillation step's target forward runs between the student's forward and
-        its backward, train_t2v_turbo_v1_lora.py:1022-1190) — separate buffers, same frozen weights."""
-        slot = "enc" if forward_only else "grad"
-        if getattr(self._engine_box, slot) is None:
-            from . import lora
-            from .engine_unet_bwd import UNetGradEngine
-            make_ops = getattr(self, "_native_ops_factory", None)  # tests substitute the emulated backend
-            if make_ops is None:
-                from .native import HipOps as make_ops
-            eng = UNetGradEngine(self, make_ops())
-            eng.checkpoint_blocks = self.native_checkpoint
-            eng.native_conditioning = self.native_conditioning
-            eng.bind_lora(lora.lora_parameters(self))
-            setattr(self._engine_box, slot, eng)
-        return getattr(self._engine_box, slot)
-
-    def _forward_native_train(self, x, timesteps, context, fps, timestep_cond, motion_cond):
-        if not (x.is_cuda or getattr(self, "_native_ops_factory", None) is not None):
-            raise RuntimeError('native_mode = "train" needs CUDA tensors')
-        if context is None:
-            raise ValueError("native LoRA training needs the text context")
-        grad = torch.is_grad_enabled()
-        eng = self.native_train_engine(forward_only=not grad)
-        from .nn_util import walk_parameters
-        trainable = {id(p) for p in walk_parameters(self) if p.requires_grad}
-        if trainable - eng.lora_ids:
-            raise RuntimeError('native_mode = "train": only LoRA tensors may require grad (the base weights are frozen packs)')
-        if context.requires_grad or (timestep_cond is not None and timestep_cond.requires_grad):
-            raise RuntimeError('native_mode = "train": gradients flow to the latents and the LoRA tensors only')
-        owns = eng.owns_conditioning(x.shape[0])
-        emb_all = None if owns else self.conditioning_emb_all(timesteps, fps, timestep_cond, motion_cond)
-        args = (timesteps, context, fps, timestep_cond, motion_cond)
-        if not grad:
-            return eng.forward_tape(x, *args, emb_all=emb_all)
-        leaves = [p for mod in eng.engine_leaves(conditioning=owns) for p in (mod.lora_up.weight, mod.lora_down.weight)]
-        return _NativeStudent.apply(x, emb_all, self, args, *leaves)
 
     def _embedding(self, timesteps, fps, timestep_cond, motion_cond):
         """Time (+ guidance-scale, + motion) and fps embedding, one row per clip (openaimodel3d.py:683-706)."""

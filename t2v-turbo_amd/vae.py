@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .nn_util import EngineBox
+from .bridge import EngineBox, _NativeDecodeGrad, needs_grad
 
 
 def Normalize(in_channels, num_groups=32):
@@ -228,30 +228,6 @@ class DiagonalGaussianDistribution:
         return self.mean
 
 
-class _NativeDecodeGrad(torch.autograd.Function):
-    """decode(z) with a native backward: forward and dX both run on the HIP engine (engine_vae_bwd.py)."""
-
-    @staticmethod
-    def forward(ctx, z, vae):
-        ctx.vae = vae
-        ctx.z_dtype = z.dtype
-        eng = vae.native_grad_engine()
-        out = eng.decode_frames_tape(z.detach().unsqueeze(2), scale=1.0).squeeze(2)
-        ctx.plan = eng._last
-        ctx.fwd_id = eng._last["fwd_id"]
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        eng = ctx.vae.native_grad_engine()
-        if ctx.plan["fwd_id"] != ctx.fwd_id:
-            raise RuntimeError("native VAE decode gradient keeps ONE outstanding decode per input shape: another decode of "
-                               "the same shape ran before this backward (set vae.native_mode = 'off' for the torch path)")
-        eng._last = ctx.plan
-        dz = eng.backward(grad_out.unsqueeze(2)).squeeze(2)
-        return dz.to(ctx.z_dtype), None
-
-
 class AutoencoderKL(nn.Module):
     """encode(x) -> posterior; decode(z) -> image (lvdm/models/autoencoder.py:13-113)."""
 
@@ -274,9 +250,8 @@ class AutoencoderKL(nn.Module):
         return self.post_quant_conv.weight.dtype
 
     def _native_ok(self, t):
-        if getattr(self, "native_mode", "auto") == "off":  # "off": every entry point takes the torch path
-            return False
-        return t.is_cuda and not (torch.is_grad_enabled() and (t.requires_grad or any(p.requires_grad for p in self.parameters())))
+        """A call on ``t`` goes to a native engine: CUDA, mode not "off" (then every entry point takes the torch path), nobody wants a gradient."""
+        return t.is_cuda and getattr(self, "native_mode", "auto") != "off" and not (torch.is_grad_enabled() and needs_grad(self, t))
 
     def encode(self, x, **kwargs):
         if self._native_ok(x):
@@ -287,43 +262,28 @@ class AutoencoderKL(nn.Module):
         """(b,3,t,H,W) -> posterior parameters (b, 2*embed, t, H/8, W/8) for all frames in one batched pass
         (the reference encodes 8-frame chunks, train_t2v_turbo_v1_lora.py:959-966)."""
         if self._native_ok(x):
-            if self._engine_box.enc is None:
-                from .engine_vae import VAEEncodeEngine
-                from .native import HipOps
-                self._engine_box.enc = VAEEncodeEngine(self, HipOps())
-            return self._engine_box.enc.encode_frames(x)
+            return self._engine_box.get("enc", "engine_vae.VAEEncodeEngine", self).encode_frames(x)
         return torch.stack([self.quant_conv(self.encoder(x[:, :, i])) for i in range(x.shape[2])], dim=2)
 
     def decode(self, z, **kwargs):
-        if getattr(self, "native_mode", "auto") == "off":
-            return self.decoder(self.post_quant_conv(z))
-        if z.is_cuda and not (torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in self.parameters()))):
+        if self._native_ok(z):
             return self.native_engine().decode_frames(z.unsqueeze(2), scale=1.0).squeeze(2)
         if (z.is_cuda and torch.is_grad_enabled() and z.requires_grad and not any(p.requires_grad for p in self.parameters())
                 and not self.training and getattr(self, "native_mode", "auto") != "off"):
             # reward-gradient branch (train_t2v_turbo_v1_lora.py:1047-1098): frozen VAE, gradient w.r.t. the latents only
-            return _NativeDecodeGrad.apply(z, self)
+            return _NativeDecodeGrad.apply(z, self.native_grad_engine())
         return self.decoder(self.post_quant_conv(z))
 
     def native_grad_engine(self):
-        if self._engine_box.grad is None:
-            from .engine_vae_bwd import VAEDecodeGradEngine
-            from .native import HipOps
-            self._engine_box.grad = VAEDecodeGradEngine(self, HipOps())
-        return self._engine_box.grad
+        return self._engine_box.get("grad", "engine_vae_bwd.VAEDecodeGradEngine", self)
 
     def native_engine(self):
-        if self._engine_box.engine is None:
-            from .engine_vae import VAEDecodeEngine
-            from .native import HipOps
-            self._engine_box.engine = VAEDecodeEngine(self, HipOps())
-        return self._engine_box.engine
+        return self._engine_box.get("engine", "engine_vae.VAEDecodeEngine", self)
 
     def decode_video(self, z, scale_factor=0.18215):
         """(b,4,t,h,w) latents -> (b,3,t,8h,8w): ``LatentDiffusion.decode_first_stage_2DAE``
         (lvdm/models/ddpm3d.py:666-679) with every frame in one batched pass on the GPU."""
-        if (z.is_cuda and getattr(self, "native_mode", "auto") != "off"
-                and not (torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in self.parameters())))):
+        if self._native_ok(z):
             return self.native_engine().decode_frames(z, scale=1.0 / scale_factor)
         z = z / scale_factor
         return torch.cat([self.decode(z[:, :, i]).unsqueeze(2) for i in range(z.shape[2])], dim=2)
