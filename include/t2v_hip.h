@@ -532,6 +532,28 @@ int t2v_quant8_blockwise(const float* x, long long n, const float* code, unsigne
 int t2v_dequant8_blockwise(const unsigned char* codes, const float* absmax, const float* code, float* out, long long n,
                            void* stream);
 
+/* ---------------------------------------------------------------- EMA of many tensors in one launch (optim.update_ema)
+ * The target network of train_latent_t2v_turbo_v2.py --use_target_unet (:1272-1276) follows the student by update_ema
+ * (utils/common_utils.py:307-319): targ.mul_(rate).add_(src.to(targ.dtype), alpha = 1 - rate) over every parameter pair, ~ 3 000
+ * small launches.  t2v_ema_multi updates MANY tensors in one launch, where they are.  `table` is a DEVICE array of n_tensors
+ * descriptors ordered by work0 (8-byte aligned): the launch covers work blocks [0, n_blocks), tensor i owning
+ * [work0, work0 + ceil(n / T2V_EMA_BLOCK)); a work block that no tensor owns touches nothing.  Targets are contiguous fp32, sources
+ * contiguous fp32 or bf16 (widened first, exactly).  A tensor whose target and source are both 16-byte aligned moves in 16-byte
+ * accesses, any other one in scalar accesses (chosen in the kernel, per tensor: parameters may be 4-byte-aligned views); tails are
+ * handled per element and nothing outside [target, target + n) is written.  Arithmetic: per element t = t * rate + s * (1.0f - rate),
+ * the expression of t2v_ema_update: on one build both give the same bits for the same data.
+ * T2V_EINVAL: NULL table, n_tensors <= 0, n_blocks <= 0. */
+#define T2V_EMA_BLOCK 4096
+typedef struct t2v_ema_tensor {
+    float* target;        /* fp32, contiguous, updated in place */
+    const void* src;      /* contiguous, same element count */
+    long long n;          /* elements */
+    long long work0;      /* first work block of this tensor in this launch */
+    int src_dt;           /* T2V_F32 or T2V_BF16 (the reference's src.to(targ.dtype)) */
+    int reserved;
+} t2v_ema_tensor;
+int t2v_ema_multi(const t2v_ema_tensor* table /* device */, int n_tensors, long long n_blocks, float rate, void* stream);
+
 /* ---------------------------------------------------------------- LoRA training path (utils/lora.py:45-50,124-129,204-209)
  * t2v_gather_f32: indexed re-layout of fp32 data.  accumulate = 0: out[i] = idx[i] >= 0 ? alpha*src[idx[i]] : 0;
  * accumulate = 1: out[i] += alpha*src[idx[i]] where idx[i] >= 0.  out is fp32 (T2V_F32) or bf16 (T2V_BF16).

@@ -57,8 +57,9 @@ def huber_loss(pred, target, huber_c=0.001):
 
 @torch.no_grad()
 def update_ema(target_params, source_params, rate=0.99):
-    for targ, src in zip(target_params, source_params):
-        targ.detach().mul_(rate).add_(src.to(targ.dtype), alpha=1 - rate)
+    """utils/common_utils.py:307-319.  ``optim.update_ema``: the same torch expression on CPU tensors, one launch on the GPU."""
+    from .optim import update_ema as _update
+    _update(target_params, source_params, rate)
 
 
 class DDIMSolver:

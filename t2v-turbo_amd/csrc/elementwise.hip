@@ -389,6 +389,7 @@ __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, long 
     }
 }
 __global__ void ema_kernel(float* t, const float* s, float rate, long long n) {
+#pragma clang fp contract(off)   // (two products and a sum, as this kernel has always been compiled: ema_multi_kernel must give the same bits)
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) t[i] = t[i] * rate + s[i] * (1.0f - rate);
 }
@@ -633,6 +634,111 @@ extern "C" int t2v_dequant8_blockwise(const unsigned char* codes, const float* a
     const long long nblocks = (n + T2V_ADAMW8_BLOCK - 1) / T2V_ADAMW8_BLOCK;
     hipLaunchKernelGGL(dequant8_kernel, dim3(blocks8(nblocks)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)codes, absmax,
                        code, out, n, nblocks);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+// ---- EMA of MANY tensors in one launch (optim.update_ema) -----------------------------------------------
+// One workgroup per work block of T2V_EMA_BLOCK elements of ONE tensor, found by binary search over work0 (wave-uniform: scalar
+// loads of a table that stays in cache).  A lane keeps T2V_EMA_BLOCK / 256 = 16 elements: four 16-byte loads of the target and four
+// (fp32) or two (bf16) of the source are issued before the first result is needed.  Pure stream: no LDS, no atomics.  The element
+// expression is ema_kernel's, written the same way and like it without floating-point contraction (two rounded products and a
+// rounded sum), so that both give the same bits.
+namespace {
+__device__ __forceinline__ float4 ema4(float4 t, const float* s, float rate) {
+#pragma clang fp contract(off)
+    t.x = t.x * rate + s[0] * (1.0f - rate);
+    t.y = t.y * rate + s[1] * (1.0f - rate);
+    t.z = t.z * rate + s[2] * (1.0f - rate);
+    t.w = t.w * rate + s[3] * (1.0f - rate);
+    return t;
+}
+__global__ __launch_bounds__(256) void ema_multi_kernel(const t2v_ema_tensor* __restrict__ table, int nt, long long nblocks, float rate) {
+#pragma clang fp contract(off)
+    constexpr int Q = T2V_EMA_BLOCK / (256 * 4);   // 4-element groups per lane and work block
+    static_assert(Q >= 2 && Q % 2 == 0 && Q * 256 * 4 == T2V_EMA_BLOCK, "T2V_EMA_BLOCK: an even number of float4 per lane");
+    const int tid = threadIdx.x;
+    for (long long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        int lo = 0, hi = nt - 1;   // the tensor that owns this work block: the last one with work0 <= blk
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[mid].work0 <= blk) lo = mid; else hi = mid - 1;
+        }
+        const t2v_ema_tensor d = table[lo];
+        const long long e0 = (blk - d.work0) * T2V_EMA_BLOCK;
+        if (e0 < 0 || e0 >= d.n) continue;   // a work block no tensor owns (a gap in work0): nothing is touched
+        const long long left = d.n - e0;
+        const int cnt = left < T2V_EMA_BLOCK ? (int)left : T2V_EMA_BLOCK;   // elements of this work block; every index below is < cnt
+        float* t = d.target + e0;
+        const bool bf = d.src_dt == T2V_BF16;
+        if ((((uintptr_t)d.target | (uintptr_t)d.src) & 15) != 0) {   // a 4-byte-aligned view: scalar accesses
+            if (bf) {
+                const bf16_t* s = (const bf16_t*)d.src + e0;
+#pragma unroll 1
+                for (int i = tid; i < cnt; i += 256) t[i] = t[i] * rate + bf2f(s[i]) * (1.0f - rate);
+            } else {
+                const float* s = (const float*)d.src + e0;
+#pragma unroll 1
+                for (int i = tid; i < cnt; i += 256) t[i] = t[i] * rate + s[i] * (1.0f - rate);
+            }
+        } else if (bf) {   // (work blocks start at multiples of 4096 elements: t + e0 and s + e0 keep the 16-byte alignment)
+            const bf16_t* s = (const bf16_t*)d.src + e0;
+            float4 T[Q];
+            uint4 S[Q / 2];
+#pragma unroll
+            for (int j = 0; j < Q / 2; ++j) {
+                const int i = (j * 256 + tid) * 8;
+                if (i + 8 <= cnt) {
+                    T[2 * j] = *(const float4*)(t + i);
+                    T[2 * j + 1] = *(const float4*)(t + i + 4);
+                    S[j] = *(const uint4*)(s + i);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < Q / 2; ++j) {
+                const int i = (j * 256 + tid) * 8;
+                if (i + 8 <= cnt) {
+                    float f[8];
+                    unpack8(S[j], f);
+                    *(float4*)(t + i) = ema4(T[2 * j], f, rate);
+                    *(float4*)(t + i + 4) = ema4(T[2 * j + 1], f + 4, rate);
+                } else {
+#pragma unroll 1
+                    for (int k = i; k < cnt; ++k) t[k] = t[k] * rate + bf2f(s[k]) * (1.0f - rate);
+                }
+            }
+        } else {
+            const float* s = (const float*)d.src + e0;
+            float4 T[Q], S[Q];
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                const int i = (j * 256 + tid) * 4;
+                if (i + 4 <= cnt) {
+                    T[j] = *(const float4*)(t + i);
+                    S[j] = *(const float4*)(s + i);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                const int i = (j * 256 + tid) * 4;
+                if (i + 4 <= cnt) {
+                    *(float4*)(t + i) = ema4(T[j], (const float*)&S[j], rate);
+                } else {
+#pragma unroll 1
+                    for (int k = i; k < cnt; ++k) t[k] = t[k] * rate + s[k] * (1.0f - rate);
+                }
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int t2v_ema_multi(const t2v_ema_tensor* table, int n_tensors, long long n_blocks, float rate, void* stream) {
+    T2V_REQUIRE(table && n_tensors > 0 && n_blocks > 0, T2V_EINVAL, "t2v_ema_multi");
+    T2V_REQUIRE((uintptr_t)table % 8 == 0, T2V_ESHAPE, "t2v_ema_multi: the table must be 8-byte aligned");
+    // grid-stride over the work blocks: up to 32 workgroups per CU of a 256-CU part, four rounds of the 8 that are resident at once
+    const unsigned grid = (unsigned)(n_blocks < 8192 ? n_blocks : 8192);
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, table, n_tensors, n_blocks, rate);
     T2V_CHECK_LAUNCH();
     return T2V_OK;
 }

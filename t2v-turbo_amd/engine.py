@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import native as nt
 from .native import on_tensor_device
-from .packs import Packer, effective_weight_bias, is_lora_leaf, leaf_out_channels, params_fingerprint  # noqa: F401  (re-exported)
+from .packs import Packer, effective_weight_bias, is_lora_leaf, leaf_out_channels, params_fingerprint, params_fingerprints  # noqa: F401  (re-exported)
 from .unet3d import (Downsample, ResBlock, SpatialTransformer, TemporalTransformer, TimestepEmbedSequential,
                      Upsample)
 
@@ -102,7 +102,9 @@ class _Engine:
         self.native = getattr(ops, "is_native", False)   # launch lists are recorded and replayed; else (emulation, tests) the closures re-run
         self.adt = ops.act_dtype
         self.plans = {}
-        self.fingerprint = None
+        self.fingerprint = None          # (structure, version) of the parameters the plans and packs were made from (``_check_weights``)
+        self.counters = {"recorded": 0, "refreshed": 0}   # plans recorded / pack refreshes run, over the engine's life
+        self.pk_refresh = {}             # refresh state of the shared Packer (``_refresh_packs``); made and dropped with it
         self.use_graph = os.environ.get("T2V_HIP_GRAPH", "0") == "1"
 
     # ---- helpers bound to the current recording -------------------------------------------------
@@ -110,12 +112,14 @@ class _Engine:
         """Start a recording.  Every plan OWNS what its launch list points at (``_own``): the recorded arguments are raw device
         pointers, so the buffers must outlive the plan, not just the recording (a second input signature used to free the first
         plan's pool, and going back to the first one replayed into reused memory).  Packed weights are shared by the plans of
-        one weight version (``_check_weights`` drops all plans when a parameter changes)."""
+        one parameter structure (``_check_weights`` drops all plans when it changes, and re-fills the packs in place — or drops the
+        plans as well, ``refresh_on_update`` — when only the values moved)."""
         self.device = device
         self.pool = BufferPool(device)
         pk = getattr(self, "pk", None)
         if not (self.plans and pk is not None and pk.device == device and pk.merge_lora and pk.wdtype == self.adt):
             self.pk = Packer(self.adt, device)
+            self.pk_refresh = {}       # (a captured refresh holds the old Packer's pointers: it goes with it)
         self.keep = []
 
     def _own(self, plan):
@@ -387,11 +391,66 @@ class _Engine:
         return True
 
     # ---- plan management --------------------------------------------------------------------------------
+    # What a parameter change costs.  The STRUCTURE changed (a parameter re-homed, replaced, cast, added, removed): the plans and the
+    # Packer go, the next call records again.  Only the VERSION counters moved (an in-place update: ``optim.update_ema``, the
+    # reference's own ``mul_().add_()`` loop, ``load_state_dict``, an optimizer step on a network that is then called under
+    # ``no_grad``): with ``refresh_on_update`` every plan, its pool and its hipGraph stay and the packs their launch lists point at
+    # are re-filled in place (``Packer.refresh``) — the EMA target of train_latent_t2v_turbo_v2.py --use_target_unet
+    # (:1238-1245, :1272-1276) moves after EVERY optimizer step and used to be packed, recorded and captured again each time.
+    # Engines that leave the switch off (the VAE engines; the gradient engines, which refresh per plan or skip their LoRA tensors)
+    # drop their plans on any change, as before.
+    refresh_on_update = False
+
     def _check_weights(self, module, skip=()):
-        fp = params_fingerprint(module, skip)
-        if fp != self.fingerprint:
-            self.plans.clear()
-            self.fingerprint = fp
+        fp = params_fingerprints(module, skip)
+        old, self.fingerprint = self.fingerprint, fp
+        if fp == old:
+            return
+        pk = getattr(self, "pk", None)
+        if self.refresh_on_update and old is not None and old[0] == fp[0] and self.plans and pk is not None:
+            self._refresh_packs(pk, self.pk_refresh, module)
+            self.counters["refreshed"] += 1
+            return
+        self.plans.clear()
+
+    # The refresh is ~ 2 000 small launches (torch copies / casts, library transposes and repacks) over FIXED tensors — the parameters'
+    # storages in, the packs out — so after one eager pass it is captured as ONE hipGraph and replayed per weight update: the host's
+    # 15-17 ms of issuing it (profiles/r06_full_finetune_wgrad_affine_rework_ab.jsonl, refresh_graph 0 / 1) go.  The graph holds raw
+    # pointers: its signature names the Packer, every pack tensor and every parameter storage, and it is dropped and re-captured when a
+    # parameter was re-homed or a pack was added (a later recording on a shared Packer); T2V_REFRESH_GRAPH=0 keeps the eager loop.
+    refresh_graph = os.environ.get("T2V_REFRESH_GRAPH", "1") == "1"
+
+    def _refresh_packs(self, pk, holder, module):
+        """Re-fill every pack of ``pk`` in place from the current parameters of ``module``.  ``holder["refresh"]`` keeps the state of
+        the three-phase pass where whoever owns ``pk`` keeps it (a full fine-tuning plan; the inference engine itself): first pass
+        eager, second pass captured, later passes replayed as one hipGraph."""
+        dev = getattr(self, "device", None)
+        if not (self.refresh_graph and self.native and dev is not None and dev.type == "cuda"):
+            pk.refresh(self.ops)
+            return
+        from .nn_util import walk_parameters
+        sig = (id(pk), pk.pointers(), tuple(p.data_ptr() for p in walk_parameters(module)))
+        st = holder.get("refresh")
+        if st is not None and st["sig"] == sig and st["graph"] is not None:
+            st["graph"].replay()
+            return
+        if st is None or st["sig"] != sig:
+            pk.refresh(self.ops)                    # first pass for this set of tensors: eager (it also warms the allocator)
+            holder["refresh"] = {"sig": sig, "graph": None, "failed": False}
+            return
+        if st["failed"]:
+            pk.refresh(self.ops)
+            return
+        try:                                         # second pass: capture, then run the captured pass
+            g = self._capture(lambda: pk.refresh(self.ops), dev)
+            g.replay()
+            st["graph"] = g
+        except Exception as e:  # noqa: BLE001 - a maker the capture cannot take (host read-back, pageable copy): stay eager, say so once
+            import warnings
+            warnings.warn(f"pack refresh not capturable as a hipGraph ({type(e).__name__}: {e}); staying with the eager pass")
+            st["failed"] = True
+            torch.cuda.synchronize(dev)
+            pk.refresh(self.ops)
 
     # ---- plan lifecycle: record the launch lists once, then refresh the static inputs and replay ----------------------
     # A plan is a plain dict: "static" (the input buffers the lists read), the outputs, and per list ("rec", and "rec_bwd" of a
@@ -415,6 +474,7 @@ class _Engine:
                 plan["fn" + key[3:]] = fn
             lists[0][1]()
         plan["pool_bytes"] = self.pool.bytes
+        self.counters["recorded"] += 1
         return plan
 
     def _adopt(self, key, plan):
@@ -542,6 +602,7 @@ class UNetEngine(_Engine):
         # the inference engine takes GroupNorm statistics from the producing GEMMs' epilogues and folds the LayerNorms into the
         # GEMMs that consume them (the gradient engine, a subclass, keeps the standalone kernels: its tape saves their inputs)
         if type(self) is UNetEngine:
+            self.refresh_on_update = True   # in-place weight updates re-fill the packs, the plans stay (``_check_weights``)
             self.fuse_gn = os.environ.get("T2V_FUSE_GN", "1") == "1"
             self.fold_ln = os.environ.get("T2V_FOLD_LN", "1") == "1"
             self.fuse_ff = os.environ.get("T2V_FUSE_FF", "0") == "1"
@@ -587,8 +648,9 @@ class UNetEngine(_Engine):
         # 1 ms per walk, instead of never)
         from .nn_util import walk_modules
         cache = getattr(self, "_dropout_mods", None)
-        if cache is None or cache[0] != self.fingerprint or cache[2] >= 64:
-            cache = self._dropout_mods = [self.fingerprint, [mod for mod in walk_modules(self.model) if isinstance(mod, nn.Dropout)], 0]
+        key = self.fingerprint if not self.refresh_on_update else self.fingerprint[0]   # (kept plans: per parameter structure)
+        if cache is None or cache[0] != key or cache[2] >= 64:
+            cache = self._dropout_mods = [key, [mod for mod in walk_modules(self.model) if isinstance(mod, nn.Dropout)], 0]
         cache[2] += 1
         return any(mod.training and mod.p > 0 for mod in cache[1])
 

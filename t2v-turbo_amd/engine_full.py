@@ -27,8 +27,6 @@ them.  Same gradients bit for bit (tests/test_unet_full_ckpt_cpu.py, tests/test_
 Correctness first: im2col is materialised (2 taps C bytes per output row) and every leaf's gradient is its own launches; the step is
 not a measured configuration of bench.py.  Verified on CPU against torch autograd through the module (tests/test_unet_full_grad_cpu.py),
 on the host simulator per kernel, and on MI355X against the imported reference's own parameter gradients (tests/golden/unet_tiny_full_grad.npz)."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -116,43 +114,12 @@ class FullTrainMixin:
         last = getattr(self, "_last", None)
         return None if last is None else last.get("refresh")
 
-    # The refresh is ~ 2 000 small launches (torch copies / casts, library transposes and repacks) over FIXED tensors — the parameters'
-    # storages in, the packs out — so after one eager pass it is captured as ONE hipGraph and replayed per optimizer step: the host's
-    # 15-17 ms of issuing it (profiles/r06_full_finetune_wgrad_affine_rework_ab.jsonl, refresh_graph 0 / 1) go.  The graph holds raw
-    # pointers: its signature names the Packer, every pack tensor and every parameter storage, and it is dropped and re-captured when a
-    # parameter was re-homed or a pack was added; T2V_REFRESH_GRAPH=0 keeps the eager loop.
-    refresh_graph = os.environ.get("T2V_REFRESH_GRAPH", "1") == "1"
-
+    # The pass itself is ``_Engine._refresh_packs`` (eager, then captured as ONE hipGraph and replayed per optimizer step), shared with
+    # the inference engine; here its state lives in the plan, next to the Packer the plan owns.
     def _refresh(self, plan):
         pk = plan["owned"][1]
         assert pk is self.pk, "the pack refresh runs on the Packer of the plan being replayed (full_activate)"
-        dev = getattr(self, "device", None)
-        if not (self.refresh_graph and self.native and dev is not None and dev.type == "cuda"):
-            pk.refresh(self.ops)
-            return
-        from .nn_util import walk_parameters
-        sig = (id(pk), pk.pointers(), tuple(p.data_ptr() for p in walk_parameters(self.model)))
-        st = plan.get("refresh")
-        if st is not None and st["sig"] == sig and st["graph"] is not None:
-            st["graph"].replay()
-            return
-        if st is None or st["sig"] != sig:
-            pk.refresh(self.ops)                    # first pass for this set of tensors: eager (it also warms the allocator)
-            plan["refresh"] = {"sig": sig, "graph": None, "failed": False}
-            return
-        if st["failed"]:
-            pk.refresh(self.ops)
-            return
-        try:                                         # second pass: capture, then run the captured pass
-            g = self._capture(lambda: pk.refresh(self.ops), dev)
-            g.replay()
-            st["graph"] = g
-        except Exception as e:  # noqa: BLE001 - a maker the capture cannot take (host read-back, pageable copy): stay eager, say so once
-            import warnings
-            warnings.warn(f"pack refresh not capturable as a hipGraph ({type(e).__name__}: {e}); staying with the eager pass")
-            st["failed"] = True
-            torch.cuda.synchronize(dev)
-            pk.refresh(self.ops)
+        self._refresh_packs(pk, plan, self.model)
 
     # ---- forward side: keep the leaf's input ----------------------------------------------------------------------------
     def full_save(self, mods, x, **info):

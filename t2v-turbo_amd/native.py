@@ -60,6 +60,15 @@ class Adamw8Tensor(C.Structure):
                 ("work0", C.c_longlong), ("lr", C.c_float), ("weight_decay", C.c_float), ("flags", C.c_int), ("reserved", C.c_int)]
 
 
+EMA_BLOCK = 4096         # T2V_EMA_BLOCK
+
+
+class EmaTensor(C.Structure):
+    """struct t2v_ema_tensor, field for field (40 bytes)."""
+    _fields_ = [("target", C.c_void_p), ("src", C.c_void_p), ("n", C.c_longlong), ("work0", C.c_longlong), ("src_dt", C.c_int),
+                ("reserved", C.c_int)]
+
+
 class GemmDesc(C.Structure):
     """struct t2v_gemm_desc"""
     _fields_ = [
@@ -253,6 +262,7 @@ _SIGS = {
     "t2v_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]),
     "t2v_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_longlong, C.c_void_p]),
+    "t2v_ema_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
     "t2v_sumsq": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2v_adamw8_step": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
@@ -884,6 +894,12 @@ class HipOps:
 
     def ema_update(self, target, src, rate):
         self._call("t2v_ema_update", _p(target), _p(src), rate, target.numel())
+
+    def ema_multi(self, table, n_tensors, n_blocks, rate):
+        """target = target * rate + src * (1 - rate) over every tensor of ``table`` (a uint8 device tensor holding ``n_tensors``
+        ``EmaTensor`` records, ordered by ``work0``) in one launch (include/t2v_hip.h)."""
+        assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(EmaTensor)
+        self._call("t2v_ema_multi", _p(table), n_tensors, n_blocks, rate)
 
     def sumsq(self, x, ws, out):
         self._call("t2v_sumsq", _p(x), x.numel(), _p(ws), _p(out))

@@ -7,6 +7,8 @@ step is one fused HIP kernel (``t2v_adamw_step``) instead of bitsandbytes' CUDA-
 ``AdamW8bit`` (below ``FlatAdamW``) is the ``torch.optim.Optimizer`` the reference's ``--use_8bit_adam`` asks for
 (``bnb.optim.AdamW8bit``): parameters and gradients stay where the trainer put them, the two moments are stored block-wise in
 8 bits (``t2v_adamw8_step``, one launch for every tensor).  ``compat.install()`` serves it as ``bitsandbytes.optim.AdamW8bit``."""
+import operator
+
 import numpy as np
 import torch
 
@@ -107,8 +109,91 @@ def update_ema_flat(target_flat, source_flat, rate=0.99, target_params=None):
         target_params[0].add_(0.0)
 
 
+# ------------------------------------------------------------------------------------------------ EMA of a module tree
+_EMA_DTYPE = np.dtype([("target", "<u8"), ("src", "<u8"), ("n", "<i8"), ("work0", "<i8"), ("src_dt", "<i4"), ("reserved", "<i4")])  # struct t2v_ema_tensor
+_EMA_TABLES = {}      # key -> cached device table (the few most recently used: a target / student pair keeps one)
+_EMA_TABLES_MAX = 4
+
+
+def ema_table(targets, sources):
+    """The ``t2v_ema_tensor`` records of the pairs, in order -> (numpy record array, work blocks of the launch)."""
+    from .native import BF16, EMA_BLOCK, F32
+    host = np.zeros(len(targets), dtype=_EMA_DTYPE)
+    work = 0
+    for i, (t, s) in enumerate(zip(targets, sources)):
+        host[i] = (t.data_ptr(), s.data_ptr(), t.numel(), work, BF16 if s.dtype == torch.bfloat16 else F32, 0)
+        work += (t.numel() + EMA_BLOCK - 1) // EMA_BLOCK
+    return host, work
+
+
+_T = torch.Tensor
+_dtype_of, _is_cuda = operator.attrgetter("dtype"), operator.attrgetter("is_cuda")
+
+
+def _ema_key(targets, sources):
+    """What the cached plan of an update depends on: per tensor of both lists the data pointer, the element count, the dtype and
+    whether it is contiguous (device pointers are unique across the GPUs of a process, so they name the device too).  Read by C-level
+    ``map``s: this runs every step, and a Python loop over the 2 x 1 485 tensors of a UNet costs as much host time as the launch takes
+    on the device."""
+    return tuple(tuple(map(f, lst)) for lst in (targets, sources) for f in (_T.data_ptr, _T.numel, _dtype_of, _T.is_contiguous))
+
+
+def _ema_plan(targets, sources):
+    """Sort the pairs — the ones ONE t2v_ema_multi launch takes (fp32 contiguous target, fp32 / bf16 contiguous source of the same size,
+    all on one GPU) and the rest — and put the launch's descriptor table on the device.  It goes up through pinned memory, so the host
+    never waits for it, and stays there until a tensor of either list is re-homed, resized or cast (``_ema_key``)."""
+    native, rest, dev = [], [], None
+    for i, (t, s) in enumerate(zip(targets, sources)):
+        ok = (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and s.device == t.device and s.is_contiguous()
+              and s.dtype in (torch.float32, torch.bfloat16) and s.numel() == t.numel() and t.numel() > 0
+              and (dev is None or t.device == dev))
+        if ok:
+            dev = t.device
+        (native if ok else rest).append(i)
+    plan = dict(native=native, rest=rest, dev=dev)
+    if native:
+        host, work = ema_table([targets[i] for i in native], [sources[i] for i in native])
+        pinned = torch.from_numpy(host.view(np.uint8)).pin_memory()
+        table = torch.empty(host.nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            table.copy_(pinned, non_blocking=True)
+        plan.update(table=table, pinned=pinned, work=work)   # (``pinned`` is kept: the copy may still be reading it)
+    return plan
+
+
+@torch.no_grad()
+def update_ema(target_params, source_params, rate=0.99):
+    """``update_ema`` of the reference (utils/common_utils.py:307-319; train_latent_t2v_turbo_v2.py:1272-1276 calls it after every
+    optimizer step with the target's and the student's ``parameters()``): targ = targ * rate + src * (1 - rate), the parameters left
+    where they are.  Pairs on the GPU with an fp32 contiguous target and an fp32 / bf16 contiguous source go into ONE
+    ``t2v_ema_multi`` launch; every other pair (CPU tensors, an fp16 target, a non-contiguous tensor) takes the torch expression."""
+    targets, sources = list(target_params), list(source_params)
+    n = min(len(targets), len(sources))
+    targets, sources = targets[:n], sources[:n]
+    if not any(map(_is_cuda, targets)):
+        for t, s in zip(targets, sources):
+            t.detach().mul_(rate).add_(s.to(t.dtype), alpha=1 - rate)
+        return
+    key = _ema_key(targets, sources)
+    plan = _EMA_TABLES.pop(key, None)
+    if plan is None:
+        plan = _ema_plan(targets, sources)
+    _EMA_TABLES[key] = plan                      # most recently used last
+    while len(_EMA_TABLES) > _EMA_TABLES_MAX:
+        _EMA_TABLES.pop(next(iter(_EMA_TABLES)))
+    for i in plan["rest"]:
+        t, s = targets[i], sources[i]
+        t.detach().mul_(rate).add_(s.to(t.dtype), alpha=1 - rate)
+    if plan["native"]:
+        with torch.cuda.device(plan["dev"]):
+            _shared_ops().ema_multi(plan["table"], len(plan["native"]), plan["work"], float(rate))
+        # The kernel writes through raw pointers: move one version counter so that the engines that packed the target's weights see
+        # the update (engine.params_fingerprints) and re-fill their packs, as FlatAdamW.step and update_ema_flat do.
+        targets[plan["native"][0]].detach().add_(0.0)
+
+
 # ------------------------------------------------------------------------------------------------ block-wise 8-bit AdamW
-QBLOCK = 256   # elements per quantisation block (T2V_ADAMW8_BLOCK)
+QBLOCK = 256  # elements per quantisation block (T2V_ADAMW8_BLOCK)
 
 
 def _dynamic_levels(top, decades):
