@@ -13,6 +13,11 @@
 //   (clip, pixel, head), rows fetched with the frame stride straight from the token-major
 //   buffers (no rearrange copies); tiny FLOPs, bandwidth bound.
 #include "common.h"
+#if defined(T2V_HOSTSIM) && !defined(T2V_WT_ON)   // the simulator's common.h stands in for csrc/common.h: every output store is the plain one there
+#define T2V_WT_ON(bit) 0
+template <int WT, class V> inline void t2v_store_out16(void* p, const V& v) { *(V*)p = v; }
+template <int WT, class V> inline void t2v_store_out8(void* p, const V& v) { *(V*)p = v; }
+#endif
 #include <cstdlib>
 
 // ablation bits (tools/attn_one.py --debug) only exist in a -DT2V_ATTN_ABLATE build: runtime branches inside the
@@ -259,7 +264,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
                 uint2 w;
                 w.x = pack2bf(o[db][g * 4 + 0] * inv, o[db][g * 4 + 1] * inv);
                 w.y = pack2bf(o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv);
-                *(uint2*)(op + db * 32 + g * 8) = w;
+                t2v_store_out8<T2V_WT_ON(T2V_WT_ATTENTION)>(op + db * 32 + g * 8, w);
             }
     }
 }
@@ -599,7 +604,7 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const bf16_t* __rest
                 uint2 w;
                 w.x = pack2bf(o[m][0] * inv, o[m][1] * inv);
                 w.y = pack2bf(o[m][2] * inv, o[m][3] * inv);
-                *(uint2*)(op + m * 16) = w;
+                t2v_store_out8<T2V_WT_ON(T2V_WT_ATTENTION)>(op + m * 16, w);
             }
         }
     }

@@ -99,6 +99,56 @@ __device__ __forceinline__ uint32_t dropout_keep_mask(uint64_t key, uint64_t qua
     return m;
 }
 
+// ---- cache policy of the inference step's output stores ----------------------------------------------------------------------------
+// A plain store leaves its line dirty in the XCD's L2, and the end of the kernel writes every dirty line back before the next launch
+// may start.  A write-through (`sc1`) store sends the bytes on while the kernel still works (tools/probes/boundary_wb_probe.cpp,
+// profiles/r13_boundary_writeback.csv: it shortens a producer -> consumer pair only where a wave instruction writes whole contiguous
+// runs of 16 B per lane; 8..32-byte pieces per row lose).  One bit of T2V_WT_MASK per kernel family; a family whose bit is clear keeps
+// the plain store, instruction for instruction.  Only for stores whose bytes the SAME launch never loads again: the asm form is
+// invisible to the compiler's alias analysis (it carries no "memory" clobber, so that the code around it is scheduled as around the
+// plain store).  Arithmetic in front of such a store that must keep its bits is written with explicit fmaf: the compiler's own
+// contraction was seen to change with the store's form (gn_group_kernel).  The host simulator's common.h stands in for this file: the
+// sources give it plain-store versions themselves.
+#define T2V_WT_GEMM 1        // t2v_gemm: staged (fast) and generic epilogue, row / column statistics side outputs
+#define T2V_WT_SPLITK 2      // split-K fp32 partial slabs and the reduce kernel's output
+#define T2V_WT_LINEAR_PR 4   // linear_pr epilogue (a lane writes 2 x 16 B of one row)
+#define T2V_WT_CONV_HALO 8   // conv_halo epilogue (tile80.h)
+#define T2V_WT_NORM 16       // GroupNorm apply / group kernels, LayerNorm kernels
+#define T2V_WT_ATTENTION 32  // spatial and temporal attention outputs (8 B per lane)
+#ifndef T2V_WT_MASK
+// default: the families that won the interleaved step A/B (profiles/r13_store_policy_ab.jsonl).  Split-K loses under write-through
+// (its fp32 slabs are read straight back by the reduce launch, which then finds them in no L2), conv_halo is inside the spread,
+// linear_pr and attention store 8..32-byte pieces, which the probe shows slower.
+#define T2V_WT_MASK (T2V_WT_GEMM | T2V_WT_NORM)
+#endif
+#define T2V_WT_ON(bit) (((T2V_WT_MASK) & (bit)) != 0)
+typedef unsigned t2v_u32x4_t __attribute__((ext_vector_type(4)));
+template <int WT>
+__device__ __forceinline__ void t2v_store_out16(void* p, const uint4& v) {
+    if constexpr (WT != 0) {
+        const t2v_u32x4_t r = {v.x, v.y, v.z, v.w};
+        // (s_nop 1: nothing after the string may rewrite the data registers before the store has read them)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(r));
+    } else {
+        *(uint4*)p = v;
+    }
+}
+template <int WT>
+__device__ __forceinline__ void t2v_store_out16(void* p, const float4& v) {
+    if constexpr (WT != 0) t2v_store_out16<WT>(p, make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)));
+    else *(float4*)p = v;
+}
+template <int WT>
+__device__ __forceinline__ void t2v_store_out8(void* p, const uint2& v) {
+    if constexpr (WT != 0) __hip_atomic_store((unsigned long long*)p, (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *(uint2*)p = v;
+}
+template <int WT>
+__device__ __forceinline__ void t2v_store_out8(void* p, const float2& v) {
+    if constexpr (WT != 0) t2v_store_out8<WT>(p, make_uint2(__float_as_uint(v.x), __float_as_uint(v.y)));
+    else *(float2*)p = v;
+}
+
 // host side
 void t2v_set_error(const char* msg);
 const void* t2v_zero_page();  // >= 256 B of device zeros (lazily allocated per process)

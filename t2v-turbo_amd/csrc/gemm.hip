@@ -25,6 +25,11 @@
 //  * workgroup id -> tile mapping is XCD-aware: each of the 8 XCDs (private L2s) gets a contiguous
 //    run of tiles, N-tile fastest, so the tiles that share an A panel hit the same L2.
 #include "common.h"
+#if defined(T2V_HOSTSIM) && !defined(T2V_WT_ON)   // the simulator's common.h stands in for csrc/common.h: every output store is the plain one there
+#define T2V_WT_ON(bit) 0
+template <int WT, class V> inline void t2v_store_out16(void* p, const V& v) { *(V*)p = v; }
+template <int WT, class V> inline void t2v_store_out8(void* p, const V& v) { *(V*)p = v; }
+#endif
 #ifdef T2V_EXPERIMENTAL
 #include "gemm2.h"
 #endif
@@ -84,12 +89,13 @@ struct Epi {
     // FAST: every run is a full, 16-byte aligned run (host-checked: vector-aligned operands, n_out % 16 == 0): the
     // per-element partial paths compile away.  The epilogue is unrolled over the wave tile, so this is most of the kernel's
     // code size, and these kernels pay for instruction fetch (a ~10 % longer epilogue measured 6 % slower end to end).
-    template <bool FAST = false>
+    // WT: cache policy of the output stores (common.h, T2V_WT_MASK); the split-K reduce kernel passes its own family's
+    template <bool FAST = false, int WT = T2V_WT_ON(T2V_WT_GEMM)>
     __device__ __forceinline__ void run(float* v, float* gate, int gm, int ch_in, int ch_out, bool has_pre = false,
                                         uint4 pre0 = uint4{0, 0, 0, 0}, uint4 pre1 = uint4{0, 0, 0, 0}) const {
         if (ch_out >= n_out) return;
         compute<FAST>(v, gate, gm, ch_in, ch_out, has_pre, pre0, pre1);
-        store<FAST>(v, gm, ch_out);
+        store<FAST, WT>(v, gm, ch_out);
     }
     // everything up to the final values of the run (v is updated in place)
     template <bool FAST = false>
@@ -174,7 +180,7 @@ struct Epi {
             for (int e = 0; e < 16; ++e) v[e] = silu_f(v[e]);
         }
     }
-    template <bool FAST = false>
+    template <bool FAST = false, int WT = T2V_WT_ON(T2V_WT_GEMM)>
     __device__ __forceinline__ void store(const float* v, int gm, int ch_out) const {
         const t2v_gemm_desc& dd = *d;
         const bool full = FAST || (vec && ch_out + 16 <= n_out);
@@ -182,7 +188,7 @@ struct Epi {
             float* op = (float*)dd.out + o_off + (long long)gm * dd.ldo + ch_out;
             if (full) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) *(float4*)(op + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+                for (int q = 0; q < 4; ++q) t2v_store_out16<WT>(op + 4 * q, make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]));
             } else {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
@@ -191,8 +197,8 @@ struct Epi {
         } else {
             bf16_t* op = (bf16_t*)dd.out + o_off + (long long)gm * dd.ldo + ch_out;
             if (full) {
-                *(uint4*)op = pack8(v);
-                *(uint4*)(op + 8) = pack8(v + 8);
+                t2v_store_out16<WT>(op, pack8(v));
+                t2v_store_out16<WT>(op + 8, pack8(v + 8));
             } else {
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
@@ -215,7 +221,7 @@ __device__ __forceinline__ void flush_slab(const char* st, int lane, bf16_t* oba
         const int r = q / LPR, c = q - r * LPR;
         const uint4 val = *(const uint4*)(st + r * P + c * 16);
         const int gm = gm0 + r, ch = col0 + c * 8;
-        if (gm < M && ch < n_out) *(uint4*)(obase + (long long)gm * ldo + ch) = val;
+        if (gm < M && ch < n_out) t2v_store_out16<T2V_WT_ON(T2V_WT_GEMM)>(obase + (long long)gm * ldo + ch, val);
     }
 }
 // ablation bit 32: same slab traffic, but the global stores sit behind a condition no finite tile meets
@@ -700,8 +706,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(WPE
                 for (int q = 0; q < 4; ++q) {
                     const int ch = ch_lane + j * 32 + 4 * q;
                     if (ch < d.N)
-                        *(float4*)(ws + (long long)gm * d.N + ch) =
-                            make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+                        t2v_store_out16<T2V_WT_ON(T2V_WT_SPLITK)>(ws + (long long)gm * d.N + ch,
+                                                                   make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]));
                 }
         }
         return;
@@ -977,13 +983,13 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(WPE
                     if constexpr (TN % 2 == 0 && WTN % 64 == 0) {
 #pragma unroll
                         for (int j = 0; j < TN; j += 2) {
-                            if (ch_lane + j * 32 + 32 < d.N) *(float4*)(rp + 2 * j) = make_float4(rs1[j], rs2[j], rs1[j + 1], rs2[j + 1]);
-                            else if (ch_lane + j * 32 < d.N) *(float2*)(rp + 2 * j) = make_float2(rs1[j], rs2[j]);
+                            if (ch_lane + j * 32 + 32 < d.N) t2v_store_out16<T2V_WT_ON(T2V_WT_GEMM)>(rp + 2 * j, make_float4(rs1[j], rs2[j], rs1[j + 1], rs2[j + 1]));
+                            else if (ch_lane + j * 32 < d.N) t2v_store_out8<T2V_WT_ON(T2V_WT_GEMM)>(rp + 2 * j, make_float2(rs1[j], rs2[j]));
                         }
                     } else {
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-                            if (ch_lane + j * 32 < d.N) *(float2*)(rp + 2 * j) = make_float2(rs1[j], rs2[j]);
+                            if (ch_lane + j * 32 < d.N) t2v_store_out8<T2V_WT_ON(T2V_WT_GEMM)>(rp + 2 * j, make_float2(rs1[j], rs2[j]));
                     }
                 }
             }
@@ -1009,7 +1015,7 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(WPE
                     a0 += __shfl_xor(a0, 32, 64); q0 += __shfl_xor(q0, 32, 64);
                     a1 += __shfl_xor(a1, 32, 64); q1 += __shfl_xor(q1, 32, 64);
                     if (hi == 0 && cpair < WTN / 2 && gm0 < d.M && col0 + 2 * cpair < d.N)
-                        *(float4*)(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col0 + 2 * cpair) * 2) = make_float4(a0, q0, a1, q1);
+                        t2v_store_out16<T2V_WT_ON(T2V_WT_GEMM)>(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col0 + 2 * cpair) * 2, make_float4(a0, q0, a1, q1));
                 }
             }
             if (ABL(32)) flush_slab_nostore<P, TN * 4>(st, lane, obase, d.ldo, m0 + wave_m * WTM + i * 32, d.M, n0 + wave_n * WTN, d.N);
@@ -1100,7 +1106,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
     }
     Epi epi;
     epi.d = &d; epi.o_off = z0 * d.o_stride0 + z1 * d.o_stride1; epi.vec = p.vec4; epi.n_out = d.N;
-    epi.run(v, nullptr, gm, ch, ch);
+    epi.run<false, T2V_WT_ON(T2V_WT_SPLITK)>(v, nullptr, gm, ch, ch);
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int BK, int WPE, bool FAST, bool RS = false, bool LNOUT = false, int FUSE = 0>

@@ -28,6 +28,11 @@
 //
 // Algorithmic work per launch: 2 M N K FLOP; bytes: M K 2 (A) + N K 2 (W, L2-resident) + M N' 2 (out) [+ M N' 2 residual].
 #include "gelu_poly.h"
+#if defined(T2V_HOSTSIM) && !defined(T2V_WT_ON)   // the simulator's common.h stands in for csrc/common.h: every output store is the plain one there
+#define T2V_WT_ON(bit) 0
+template <int WT, class V> inline void t2v_store_out16(void* p, const V& v) { *(V*)p = v; }
+template <int WT, class V> inline void t2v_store_out8(void* p, const V& v) { *(V*)p = v; }
+#endif
 #include <cstdlib>
 #include <type_traits>
 
@@ -414,8 +419,8 @@ __global__ __launch_bounds__(kLprWaves * 64) __attribute__((amdgpu_waves_per_eu(
             auto put = [&](const float* v, int row0, int col) {
                 if (row0 + (int)le < d.M && !LABL(16)) {
                     char* op = (char*)obase + ((long long)row0 * d.ldo + col) * 2 + g_off;
-                    *(uint4*)op = pack8(v);
-                    *(uint4*)(op + 16) = pack8(v + 8);
+                    t2v_store_out16<T2V_WT_ON(T2V_WT_LINEAR_PR)>(op, pack8(v));
+                    t2v_store_out16<T2V_WT_ON(T2V_WT_LINEAR_PR)>(op + 16, pack8(v + 8));
                 }
             };
             if constexpr (GEGLU) {

@@ -2,6 +2,11 @@
 // All three are HBM-bandwidth bound: 16-byte (8 x bf16) per-lane accesses, fp32 math,
 // wave-shuffle (64-lane butterfly) reductions, no re-reads beyond what the algorithm needs.
 #include "common.h"
+#if defined(T2V_HOSTSIM) && !defined(T2V_WT_ON)   // the simulator's common.h stands in for csrc/common.h: every output store is the plain one there
+#define T2V_WT_ON(bit) 0
+template <int WT, class V> inline void t2v_store_out16(void* p, const V& v) { *(V*)p = v; }
+template <int WT, class V> inline void t2v_store_out8(void* p, const V& v) { *(V*)p = v; }
+#endif
 #include <cstdlib>
 
 namespace {
@@ -386,7 +391,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* x0, int c0,
                             const float v = f[e] * sc[j][e] + sf[j][e];
                             f[e] = silu ? silu_f(v) : v;
                         }
-                        *(uint4*)(out + ((long long)unit * rows_per_unit + rr) * ldo + ci * 8) = pack8(f);
+                        t2v_store_out16<T2V_WT_ON(T2V_WT_NORM)>(out + ((long long)unit * rows_per_unit + rr) * ldo + ci * 8, pack8(f));
                     }
                 }
             }
@@ -595,7 +600,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* x, int ldx
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = (v[j][e] - mean) * rstd * gg[j][e] + bb[j][e];
-                *(uint4*)(out + (row0 + r) * ldo + ci * 8) = pack8(o);
+                t2v_store_out16<T2V_WT_ON(T2V_WT_NORM)>(out + (row0 + r) * ldo + ci * 8, pack8(o));
             }
         }
     }
@@ -658,7 +663,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* x, in
                 float o8[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o8[e] = (v[k][e] - mean) * rstd * gg[k][e] + bb[k][e];
-                *(uint4*)(out + row * ldo + (sub + k * LPR) * 8) = pack8(o8);
+                t2v_store_out16<T2V_WT_ON(T2V_WT_NORM)>(out + row * ldo + (sub + k * LPR) * 8, pack8(o8));
             }
         }
     }
@@ -924,10 +929,12 @@ __global__ __launch_bounds__(NT) void gn_group_kernel(const bf16_t* __restrict__
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float sc = rstd * gm[e];
-            const float v = f[e] * sc + (bt[e] - mean * sc);
+            // (the two fused multiply-adds spelled out: left to the compiler's contraction, the form of the store below decides
+            // whether they fuse, and the output bits with it)
+            const float v = fmaf(f[e], sc, fmaf(-mean, sc, bt[e]));
             f[e] = silu ? silu_f(v) : v;
         }
-        *(uint4*)(out + (row0 + rr[j]) * ldo + cc[j]) = pack8(f);
+        t2v_store_out16<T2V_WT_ON(T2V_WT_NORM)>(out + (row0 + rr[j]) * ldo + cc[j], pack8(f));
     }
 }
 // threads per block of that form, 0 = not eligible (channels per group not a multiple of 8, a group that straddles the two parts of a

@@ -2,6 +2,11 @@
 // the LDS-DMA helpers, the counted waits and the workgroup-level epilogue.
 #pragma once
 #include "common.h"
+#if defined(T2V_HOSTSIM) && !defined(T2V_WT_ON)   // the simulator's common.h stands in for csrc/common.h: every output store is the plain one there
+#define T2V_WT_ON(bit) 0
+template <int WT, class V> inline void t2v_store_out16(void* p, const V& v) { *(V*)p = v; }
+template <int WT, class V> inline void t2v_store_out8(void* p, const V& v) { *(V*)p = v; }
+#endif
 #include <type_traits>
 
 namespace tile80 {
@@ -78,7 +83,7 @@ __device__ __forceinline__ void epilogue(char* smem, const t2v_gemm_desc& d, f32
             if (idx >= BM * CPR) break;
             const int r = idx / CPR, c = idx - r * CPR;
             const int gm = row_tab[r], ch = n0 + c * 8;
-            if (gm >= 0 && ch < d.N && !skip_stores) *(uint4*)(obase + (long long)gm * d.ldo + ch) = *(const uint4*)(smem + r * P16 + c * 16);
+            if (gm >= 0 && ch < d.N && !skip_stores) t2v_store_out16<T2V_WT_ON(T2V_WT_CONV_HALO)>(obase + (long long)gm * d.ldo + ch, *(const uint4*)(smem + r * P16 + c * 16));
         }
         if (d.colstat_out) {
             constexpr int NSL = BM / 32, NCP = BN / 2;
@@ -94,7 +99,7 @@ __device__ __forceinline__ void epilogue(char* smem, const t2v_gemm_desc& d, f32
                     a0 += x0; q0 = fmaf(x0, x0, q0);
                     a1 += x1; q1 = fmaf(x1, x1, q1);
                 }
-                *(float4*)(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col) * 2) = make_float4(a0, q0, a1, q1);   // (host-checked: a tile-order slab is 32 consecutive global rows)
+                t2v_store_out16<T2V_WT_ON(T2V_WT_CONV_HALO)>(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col) * 2, make_float4(a0, q0, a1, q1));   // (host-checked: a tile-order slab is 32 consecutive global rows)
             }
         }
         return;
@@ -152,7 +157,7 @@ __device__ __forceinline__ void epilogue(char* smem, const t2v_gemm_desc& d, f32
             }
             const uint4 val = pack8(x);
             if (d.colstat_out) *(uint4*)(smem + r * P32 + c * 32) = val;   // the statistics are of what is stored
-            if (gm >= 0 && ch < d.N && !skip_stores) *(uint4*)(obase + (long long)gm * d.ldo + ch) = val;
+            if (gm >= 0 && ch < d.N && !skip_stores) t2v_store_out16<T2V_WT_ON(T2V_WT_CONV_HALO)>(obase + (long long)gm * d.ldo + ch, val);
         }
         if (d.colstat_out) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -171,7 +176,7 @@ __device__ __forceinline__ void epilogue(char* smem, const t2v_gemm_desc& d, f32
                     a0 += x0; q0 = fmaf(x0, x0, q0);
                     a1 += x1; q1 = fmaf(x1, x1, q1);
                 }
-                *(float4*)(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col) * 2) = make_float4(a0, q0, a1, q1);
+                t2v_store_out16<T2V_WT_ON(T2V_WT_CONV_HALO)>(d.colstat_out + ((long long)(gm0 >> 5) * d.N + col) * 2, make_float4(a0, q0, a1, q1));
             }
         }
     }
