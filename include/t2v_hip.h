@@ -277,16 +277,6 @@ int t2v_ffn_fused(const void* x, int ldx, int M, int C, const void* w1p, const f
 int t2v_conv3x3_small_cin(const void* x, int n_img, int h, int w, int cin, const float* wgt,
                           const float* bias, int cout, void* out, void* stream);
 
-#ifdef T2V_EXPERIMENTAL
-/* direct 3x3 s1 p1 conv for a tiny number of OUTPUT channels (1 <= cout <= 4; measured 4x slower than the MFMA tile): x bf16 [M][cin] (row stride ldx, cin % 8 == 0),
- * w fp32 [cout][9][cin] (tap-major), bias fp32 [cout] or NULL, out [M][cout] fp32 (out_f32 != 0) or bf16 at row stride ldo; the image
- * width must be a multiple of 4 (a thread owns four pixels of a row).  Replaces Decoder.conv_out (ae_modules.py:641: 128 -> 3 channels
- * at 320x512) — on the MFMA tiles that conv multiplies a 64-/128-wide tile of padding.  t2v_conv3x3_small_cout_supported: 1 / 0. */
-int t2v_conv3x3_small_cout_supported(int w, int cin, int cout);
-int t2v_conv3x3_small_cout(const void* x, int ldx, int n_img, int h, int w, int cin, const float* wgt, const float* bias, int cout,
-                           void* out, int ldo, int out_f32, void* stream);
-#endif
-
 /* ---------------------------------------------------------------- normalisation
  * GroupNorm(32) in two phases over token-major data with optional virtual concat.
  * A "unit" is the statistics extent: one frame (ResBlock / SpatialTransformer / VAE, 4-D input)
@@ -400,12 +390,6 @@ int t2v_lcm_step(const float* x, const void* eps, int eps_dt, const float* noise
  * compiles them out and these calls just store the value). */
 int t2v_gemm_debug(int bits);
 int t2v_attn_debug(int bits);
-#ifdef T2V_EXPERIMENTAL
-/* which form of the spatial forward t2v_attn_spatial launches (tools / tests; the product default is 0 and the others are measured no
- * faster): 0 = 4 waves x 32 queries per workgroup, 8 = 8 waves x 32, 64 = 4 waves x 64 queries (two query sets per wave, phases offset)
- * on launches with >= 512 queries and keys, 65 = that form always.  Same arithmetic per query in every form: bit-identical outputs. */
-int t2v_attn_spatial_form(int form);
-#endif
 /* t2v_group_norm has a ONE-launch form (registers hold the tensor, per-unit inter-workgroup barrier) for tensors that fit:
  * t2v_gn_coop_enable(1) / environment T2V_GN_COOP=1 selects it (default off: measured slower than the three-launch form on
  * MI355X for cache-resident tensors); t2v_gn_coop_error() returns 1 if a

@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 SOURCES = ["gemm.hip", "gemm_exp.hip", "gemm_fuse.hip", "conv_halo.hip", "linear_pr.hip", "norm.hip", "attention.hip", "elementwise.hip", "backward.hip", "backward_unet.hip", "train.hip", "attention_bwd.hip", "wgrad_tn.hip", "full_grad.hip", "replay.hip"]
-# T2V_EXPERIMENTAL=1: the library WITH the measured negative results (the second t2v_gemm kernel family, the one-launch feed-forward, the
-# alternative flash-attention forms, the direct small-Cout conv: -DT2V_EXPERIMENTAL) as libt2v_hip_exp.so next to the product library —
+# T2V_EXPERIMENTAL=1: the library WITH the measured negative results (the second t2v_gemm kernel family, the one-launch feed-forward:
+# -DT2V_EXPERIMENTAL) as libt2v_hip_exp.so next to the product library —
 # tools and tests load it through T2V_HIP_LIB; the product library and include/t2v_hip.h's default view do not carry them.
 EXPERIMENTAL = os.environ.get("T2V_EXPERIMENTAL") == "1"
 if EXPERIMENTAL:

@@ -27,13 +27,6 @@ class VAEDecodeEngine(_Engine):
     # 80-channel wave tiles.  The kernel pads the last channel tile (rows >= N are out-of-range DMA lanes = zeros, never stored):
     # 128 -> 160, 256 -> 320, 512 -> 560 / 640 columns of MFMA work.  T2V_VAE_HALO=0: the tuned t2v_gemm tiles (rounds 1-4).
     vae_halo = os.environ.get("T2V_VAE_HALO", "1") == "1"
-    # conv_out (128 -> 3 channels) by the direct small-Cout kernel (csrc/elementwise.hip, t2v_conv3x3_small_cout) instead of an MFMA tile
-    # that is 97 % padding.  MEASURED SLOWER on MI355X (round 5, same box, interleaved: decode 27.98 / 28.23 ms with it, 25.47 / 25.48 ms
-    # without, profiles/r05_vae_decode_ab.jsonl): ~3.3 ms against 0.75 ms — the matrix cores multiply the padding at 1 PFLOP/s, while the
-    # VALU form is bound by its own load -> 460-instruction chunk -> load chain at three waves per SIMD.  Opt-in (T2V_SMALL_COUT=1), kept
-    # as a tested negative result.
-    small_cout = os.environ.get("T2V_SMALL_COUT", "0") == "1"
-    small_cout_min_tokens = 1 << 18
 
     def _halo_width_ok(self, N):
         return N % 80 == 0 or (self.vae_halo and N % 16 == 0 and N >= 64)
@@ -101,14 +94,7 @@ class VAEDecodeEngine(_Engine):
                 x = nx
         tt = self.gn(x, dec.norm_out, n_img, x.h * x.w, True)
         self.pool.put(x.t)
-        n_out = leaf_out_channels(dec.conv_out)
-        if (self.small_cout and hasattr(ops, "conv_small_cout") and tt.dtype == torch.bfloat16 and n_img * x.h * x.w >= self.small_cout_min_tokens
-                and ops.conv_small_cout_supported(x.w, tt.shape[1], n_out)):
-            # conv_out (ae_modules.py:641: 128 -> 3 channels): a direct VALU conv instead of an MFMA tile that is 97 % padding
-            yt = self.buf(n_img * x.h * x.w, n_out, torch.float32)
-            ops.conv_small_cout(tt, n_img, x.h, x.w, pk.small_conv(dec.conv_out), pk.bias(dec.conv_out), yt)
-        else:
-            yt = self.conv(Act(tt, n_img, x.h, x.w), dec.conv_out, nt.GEMM_CONV3X3, out_dtype=torch.float32).t
+        yt = self.conv(Act(tt, n_img, x.h, x.w), dec.conv_out, nt.GEMM_CONV3X3, out_dtype=torch.float32).t
         self.pool.put(tt)
         ops.tokens_to_ncfhw(yt, out)
         self.pool.put(yt)

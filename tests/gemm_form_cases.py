@@ -785,16 +785,7 @@ def case_repack(ops, dev, kind, taps):
 
 def case_experimental(ops, dev, which):
     """The experimental entry points, where the loaded library exports them (the device file lists them as absent-by-design)."""
-    if which == "small_cout":
-        n_img, h, w, cin, cout = 2, 5, 8, 16, 3
-        M = n_img * h * w
-        x, wt, b = rnd(M, cin, seed=1), f32r(rnd(cout, 9 * cin, seed=2, scale=0.1)), f32r(rnd(cout, seed=3))
-        out = Out(M, cout + 5, [(1, 1 + cout)], dev, F32)
-        ops.conv_small_cout(inbuf(x, cin + 16, dev, col0=8), n_img, h, w, inflat(wt, dev), inflat(b, dev), out.views[0])
-        G = gather(x, nt.GEMM_CONV3X3, n_img, h, w)
-        ref = G @ wt.t() + b
-        close_rc("out", out.check("out")[0], ref, f32r(ref), STAT_TOL)
-    elif which == "gemm2":
+    if which == "gemm2":
         g = Gemm(dev, M=200, N=160, c0=128, residual=True, seed=71)
         ops.gemm(g.a0_d, g.w_d, g.out.views[0], **g.kw(tile_cfg=51))
         ref, slack, _ = g.reference()
@@ -813,7 +804,7 @@ def case_experimental(ops, dev, which):
         close_rc("out", out.check("out")[0], ref, bfr(ref), BWD_TOL)
 
 
-EXPERIMENTAL_ENTRIES = {"small_cout": "t2v_conv3x3_small_cout", "gemm2": "t2v_gemm2_enable", "ffn_fused": "t2v_ffn_fused"}
+EXPERIMENTAL_ENTRIES = {"gemm2": "t2v_gemm2_enable", "ffn_fused": "t2v_ffn_fused"}
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals

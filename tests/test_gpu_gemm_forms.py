@@ -3,9 +3,9 @@ split-K, batching and fused epilogues, t2v_conv_halo, t2v_linear_pr, the wgrad p
 forms with poisoned padding and guarded outputs.
 
 Not run here, by name: tile ids 24-29 (experimental; with T2V_TEST_EXPERIMENTAL_TILES=1 they run), and the experimental entry points
-t2v_conv3x3_small_cout, t2v_ffn_fused and gemm2 (t2v_gemm2_enable), which the product library does not export.
+t2v_ffn_fused and gemm2 (t2v_gemm2_enable), which the product library does not export.
 
-Measured on an MI355X: the whole file (532 tests run, the 3 experimental entries skipped) takes 4.1 s; the slowest test is
+Measured on an MI355X: the whole file (532 tests run, the 2 experimental entries skipped) takes 4.1 s; the slowest test is
 gemm-dropout-p0.1-cfg4 at 0.09 s (it also launches t2v_dropout_bf16 over the full matrix), then dropout-inplace0-resid0 0.06 s,
 wgrad-300x250x380-s0 0.04 s; module set-up (loading the library) 0.14 s."""
 import os

@@ -255,36 +255,6 @@ def test_attn_spatial_flash(pair, n_img, seq_q, seq_kv, heads, kv_div):
     assert rel_l2(got, out_e) < 8e-3  # P is rounded to bf16 before the PV product
 
 
-@pytest.mark.parametrize("n_img,seq_q,seq_kv,heads,kv_div", [(2, 700, 700, 2, 1), (4, 300, 77, 3, 2), (1, 2560, 2560, 1, 1), (2, 40, 200, 2, 1)])
-def test_attn_spatial_forms_are_bit_identical(pair, n_img, seq_q, seq_kv, heads, kv_div):
-    """t2v_attn_spatial_form: eight waves per workgroup (8) and 64 queries per wave with the two query sets' phases offset (65) do the SAME
-    arithmetic per query as the product kernel (0) — outputs must be bit-identical: ragged query blocks of 128 / 256, the last tile's
-    padding keys, per-clip text keys (kv_div), a running max that moves.  (Both are measured no faster: tools / tests only.)"""
-    from t2v_turbo_amd import native as _nt
-    if not _nt.has_experimental():
-        pytest.skip("entry point of a T2V_EXPERIMENTAL=1 build (python t2v-turbo_amd/csrc/build.py with T2V_EXPERIMENTAL=1, then T2V_HIP_LIB=.../libt2v_hip_exp.so)")
-
-    inner = heads * 64
-    n_kv = n_img // kv_div
-    kp = ((seq_kv + 63) // 64) * 64
-    q = _rt(n_img * seq_q, inner, seed=11, scale=2.0).cuda().bfloat16()
-    k = _rt(n_kv * seq_kv, inner, seed=12, scale=2.0).cuda().bfloat16()
-    vt = _rt(n_kv * inner, kp, seed=13).cuda().bfloat16()
-    vt[:, seq_kv:] = 1e30
-    outs = []
-    try:
-        for form in (0, 8, 65):
-            pair.hip.lib.t2v_attn_spatial_form(form)
-            o = torch.full((n_img * seq_q, inner), float("nan"), dtype=torch.bfloat16, device="cuda")
-            pair.hip.attn_spatial(q, k, vt, kp, o, n_img, seq_q, seq_kv, heads, kv_div, 0.125)
-            torch.cuda.synchronize()
-            outs.append(o.clone())
-    finally:
-        pair.hip.lib.t2v_attn_spatial_form(0)
-    assert torch.isfinite(outs[0].float()).all()
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-
-
 def test_attn_spatial_online_softmax_rescale(pair):
     """Force the running max to jump at a late key tile (spike one key against every query)."""
     seq, inner = 256, 64
@@ -543,27 +513,6 @@ def test_gemm_layernorm_second_output(pair, M, K, res):
     assert torch.isfinite(ln_h.float()).all()
     assert rel_l2(ln_h.float().cpu(), ln_e) < BF16_TOL
     assert rel_l2(ln_h.float().cpu(), ln_p.float().cpu()) < 2e-2   # LN of the bf16-rounded stream: the rounding of x shows when |mean| >> std
-
-
-def test_conv3x3_small_cout_direct(pair):
-    """t2v_conv3x3_small_cout at the VAE decoder's conv_out size (one 320x512 frame, 128 -> 3 channels, fp32 out) and small corner cases."""
-    from t2v_turbo_amd import native as _nt
-    if not _nt.has_experimental():
-        pytest.skip("entry point of a T2V_EXPERIMENTAL=1 build (python t2v-turbo_amd/csrc/build.py with T2V_EXPERIMENTAL=1, then T2V_HIP_LIB=.../libt2v_hip_exp.so)")
-
-    for n_img, h, w, cin, cout, f32 in [(1, 320, 512, 128, 3, True), (2, 6, 8, 16, 3, False), (1, 5, 12, 64, 4, True), (3, 3, 4, 8, 1, True)]:
-        M = n_img * h * w
-        x = _rt(M, cin, seed=cin + h)
-        wgt = _rt(cout, 9 * cin, seed=3, scale=(9 * cin) ** -0.5)
-        bias = _rt(cout, seed=4)
-        assert pair.hip.conv_small_cout_supported(w, cin, cout)
-        o_h = torch.full((M, cout), float("nan"), device="cuda", dtype=torch.float32 if f32 else torch.bfloat16)
-        o_e = torch.zeros(M, cout)
-        pair.hip.conv_small_cout(x.cuda().bfloat16().contiguous(), n_img, h, w, wgt.cuda().float().contiguous(), bias.cuda().float().contiguous(), o_h)
-        pair.emu.conv_small(x, n_img, h, w, wgt, bias, o_e)
-        torch.cuda.synchronize()
-        assert torch.isfinite(o_h.float()).all()
-        assert rel_l2(o_h.float().cpu(), o_e) < (2e-5 if f32 else BF16_TOL), (n_img, h, w, cin, cout)
 
 
 # ---------------------------------------------------------------------------------- t2v_conv_halo (csrc/conv_halo.hip)
