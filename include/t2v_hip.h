@@ -538,6 +538,58 @@ typedef struct t2v_ema_tensor {
 } t2v_ema_tensor;
 int t2v_ema_multi(const t2v_ema_tensor* table /* device */, int n_tensors, long long n_blocks, float rate, void* stream);
 
+/* ---------------------------------------------------------------- fp32 AdamW and gradient clipping of many tensors where they are
+ * (optim.AdamW, optim.clip_grad_norm_): the trainers' default optimizer side, torch.optim.AdamW over per-tensor parameters
+ * (train_latent_t2v_turbo_v2.py:787-845) after accelerator.clip_grad_norm_ (:1265-1268).  All three entry points walk ONE table: a
+ * DEVICE array of n_tensors descriptors ordered by work0 (8-byte aligned).  The launch covers work blocks [0, n_blocks), tensor i
+ * owning [work0, work0 + ceil(n / T2V_ADAMW_BLOCK)); a work block that no tensor owns touches nothing.  param, grad, exp_avg and
+ * exp_avg_sq are contiguous fp32 anywhere in memory.  Access width is chosen per tensor in the kernel: 16-byte accesses when every
+ * pointer the entry point uses is 16-byte aligned (t2v_adamw_multi: all four; the other two: grad), scalar accesses otherwise; tails
+ * are handled per element and nothing outside [ptr, ptr + n) is read or written.
+ *
+ * t2v_adamw_multi: `hyper` is a HOST array of n_hyper <= T2V_ADAMW_MAX_HYPER rows, handed to the kernel by value (a moving learning
+ * rate costs no upload; the device table changes only when a pointer does); a tensor's `hyper` field is its row (a tensor whose row
+ * is outside [0, n_hyper) is not touched).  The bias corrections are formed here, as in t2v_adamw8_step:
+ * bc1 = 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)).  Per element, every product and sum rounded on its
+ * own (no contraction), the order of the fp32-state branch of t2v_adamw8_step, whose bits it reproduces on one build:
+ *     gr = g * scale;  p *= 1 - lr * wd;  m = b1 * m + (1 - b1) * gr;  v = b2 * v + (1 - b2) * gr * gr;
+ *     p -= (lr / bc1) * m / (sqrtf(v) / bc2_sqrt + eps)
+ * with scale = grad_scale * (grad_scale_dev ? *grad_scale_dev : 1.0f): grad_scale_dev is a DEVICE scalar (the clip coefficient that
+ * t2v_sumsq_multi left there) or NULL.  T2V_EINVAL: NULL table or hyper, n_tensors <= 0, n_blocks < n_tensors, n_hyper outside
+ * 1..T2V_ADAMW_MAX_HYPER, a step < 1.  T2V_ESHAPE: a table that is not 8-byte aligned.
+ *
+ * t2v_sumsq_multi reads grad, n and work0 only.  Every work block writes one fp32 partial to ws[block] (ws: n_blocks floats; 0 for a
+ * block no tensor owns); a finishing launch adds the partials in a fixed order, in double, and writes out[0] = sqrt(sum) and
+ * out[1] = max_norm > 0 ? min(1, max_norm / (out[0] + 1e-6f)) : 1 — the coefficient of torch.nn.utils.clip_grad_norm_; a NaN norm
+ * gives a NaN coefficient, as torch.clamp does.  Deterministic: the same data gives the same bits.
+ * t2v_scale_multi: grad *= *coef_dev in place over the table; a workgroup that reads exactly 1.0f returns without touching gradient
+ * memory (bitwise the same result). */
+#define T2V_ADAMW_BLOCK 4096
+#define T2V_ADAMW_MAX_HYPER 16
+typedef struct t2v_adamw_tensor {
+    float* param;
+    float* grad;           /* read by t2v_adamw_multi and t2v_sumsq_multi, scaled in place by t2v_scale_multi */
+    float* exp_avg;
+    float* exp_avg_sq;
+    long long n;           /* elements */
+    long long work0;       /* first work block of this tensor in this launch */
+    int hyper;             /* row of the launch's t2v_adamw_hyper array */
+    int reserved;
+} t2v_adamw_tensor;
+typedef struct t2v_adamw_hyper {
+    float lr;
+    float weight_decay;
+    float beta1;
+    float beta2;
+    float eps;
+    int step;              /* >= 1: the step being taken (bias correction) */
+} t2v_adamw_hyper;
+int t2v_adamw_multi(const t2v_adamw_tensor* table /* device */, int n_tensors, long long n_blocks, const t2v_adamw_hyper* hyper /* host */,
+                    int n_hyper, float grad_scale, const float* grad_scale_dev, void* stream);
+int t2v_sumsq_multi(const t2v_adamw_tensor* table /* device */, int n_tensors, long long n_blocks, float* ws, float max_norm, float* out,
+                    void* stream);
+int t2v_scale_multi(const t2v_adamw_tensor* table /* device */, int n_tensors, long long n_blocks, const float* coef_dev, void* stream);
+
 /* ---------------------------------------------------------------- LoRA training path (utils/lora.py:45-50,124-129,204-209)
  * t2v_gather_f32: indexed re-layout of fp32 data.  accumulate = 0: out[i] = idx[i] >= 0 ? alpha*src[idx[i]] : 0;
  * accumulate = 1: out[i] += alpha*src[idx[i]] where idx[i] >= 0.  out is fp32 (T2V_F32) or bf16 (T2V_BF16).

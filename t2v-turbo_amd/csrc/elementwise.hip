@@ -636,6 +636,247 @@ extern "C" int t2v_ema_multi(const t2v_ema_tensor* table, int n_tensors, long lo
     return T2V_OK;
 }
 
+// ---- fp32 AdamW, gradient norm and gradient scaling of MANY tensors where they are (optim.AdamW, optim.clip_grad_norm_) ----
+// One workgroup per work block of T2V_ADAMW_BLOCK elements of ONE tensor (binary search over work0, as above); persistent grid.  A
+// lane keeps T2V_ADAMW_BLOCK / 256 = 16 elements of each of the four arrays: all sixteen 16-byte loads are issued before the first
+// result is needed.  Pure stream, 28 B per element: no LDS, no atomics.  The element expression is the fp32-state branch of
+// adamw8_kernel, written the same way and like it without floating-point contraction: on one build both give the same bits.
+namespace {
+struct AdamwRows {   // the hyper rows of one launch, by value in the kernel arguments: a moving lr costs no upload
+    float lr[T2V_ADAMW_MAX_HYPER], wd[T2V_ADAMW_MAX_HYPER], b1[T2V_ADAMW_MAX_HYPER], b2[T2V_ADAMW_MAX_HYPER], eps[T2V_ADAMW_MAX_HYPER],
+        bc1[T2V_ADAMW_MAX_HYPER], bc2_sqrt[T2V_ADAMW_MAX_HYPER];
+};
+struct AdamwK { float scale, decay, b1, b2, step_size, bc2_sqrt, eps; };
+__device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, const AdamwK& k) {
+#pragma clang fp contract(off)
+    const float gr = g * k.scale;   // t2v_adamw_step's order of operations
+    p *= k.decay;
+    m = k.b1 * m + (1.0f - k.b1) * gr;
+    v = k.b2 * v + (1.0f - k.b2) * gr * gr;
+    p -= k.step_size * m / (sqrtf(v) / k.bc2_sqrt + k.eps);
+}
+// the tensor that owns work block `blk`: the last one with work0 <= blk
+template <class T>
+__device__ __forceinline__ int owner_of(const T* table, int nt, long long blk) {
+    int lo = 0, hi = nt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].work0 <= blk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const t2v_adamw_tensor* __restrict__ table, int nt, long long nblocks,
+                                                          AdamwRows rows, int n_rows, float gscale, const float* gscale_dev) {
+#pragma clang fp contract(off)
+    constexpr int Q = T2V_ADAMW_BLOCK / (256 * 4);   // 4-element groups per lane and work block
+    static_assert(Q >= 1 && Q * 256 * 4 == T2V_ADAMW_BLOCK, "T2V_ADAMW_BLOCK: whole float4 per lane");
+    const int tid = threadIdx.x;
+    const float scale = gscale * (gscale_dev ? *gscale_dev : 1.0f);
+    for (long long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const t2v_adamw_tensor d = table[owner_of(table, nt, blk)];
+        const long long e0 = (blk - d.work0) * T2V_ADAMW_BLOCK;
+        if (e0 < 0 || e0 >= d.n || d.hyper < 0 || d.hyper >= n_rows) continue;   // a work block no tensor owns: nothing is touched
+        const long long left = d.n - e0;
+        const int cnt = left < T2V_ADAMW_BLOCK ? (int)left : T2V_ADAMW_BLOCK;   // elements of this work block; every index below is < cnt
+        const int h = d.hyper;
+        AdamwK k;
+        k.scale = scale;
+        k.decay = 1.0f - rows.lr[h] * rows.wd[h];
+        k.b1 = rows.b1[h]; k.b2 = rows.b2[h];
+        k.step_size = rows.lr[h] / rows.bc1[h];
+        k.bc2_sqrt = rows.bc2_sqrt[h]; k.eps = rows.eps[h];
+        float* p = d.param + e0;
+        const float* g = d.grad + e0;
+        float* m = d.exp_avg + e0;
+        float* v = d.exp_avg_sq + e0;
+        if ((((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 15) != 0) {
+#pragma unroll 1
+            for (int i = tid; i < cnt; i += 256) {   // a 4-byte-aligned view: scalar accesses
+                float pi = p[i], mi = m[i], vi = v[i];
+                adamw1(pi, g[i], mi, vi, k);
+                p[i] = pi; m[i] = mi; v[i] = vi;
+            }
+            continue;
+        }
+        // (work blocks start at multiples of 4096 elements: the four pointers keep their 16-byte alignment)
+        float4 P[Q], G[Q], M[Q], V[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int i = (j * 256 + tid) * 4;
+            if (i + 4 <= cnt) {
+                P[j] = *(const float4*)(p + i);
+                G[j] = *(const float4*)(g + i);
+                M[j] = *(const float4*)(m + i);
+                V[j] = *(const float4*)(v + i);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int i = (j * 256 + tid) * 4;
+            if (i + 4 <= cnt) {
+                adamw1(P[j].x, G[j].x, M[j].x, V[j].x, k);
+                adamw1(P[j].y, G[j].y, M[j].y, V[j].y, k);
+                adamw1(P[j].z, G[j].z, M[j].z, V[j].z, k);
+                adamw1(P[j].w, G[j].w, M[j].w, V[j].w, k);
+                *(float4*)(p + i) = P[j];
+                *(float4*)(m + i) = M[j];
+                *(float4*)(v + i) = V[j];
+            } else {
+#pragma unroll 1
+                for (int e = i; e < cnt; ++e) {   // the (at most 3) elements past the last whole float4
+                    float pe = p[e], me = m[e], ve = v[e];
+                    adamw1(pe, g[e], me, ve, k);
+                    p[e] = pe; m[e] = me; v[e] = ve;
+                }
+            }
+        }
+    }
+}
+// ws[blk] = sum of squares of the gradient elements of work block blk.  A lane adds its 16 squares one after the other, then the wave
+// shuffle tree (6 levels), then the four waves pairwise (2 levels): a fixed order, so the same data gives the same bits.
+__global__ __launch_bounds__(256) void sumsq_multi_kernel(const t2v_adamw_tensor* __restrict__ table, int nt, long long nblocks,
+                                                          float* __restrict__ ws) {
+    constexpr int Q = T2V_ADAMW_BLOCK / (256 * 4);
+    __shared__ float sh[4];
+    const int tid = threadIdx.x;
+    for (long long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const t2v_adamw_tensor d = table[owner_of(table, nt, blk)];
+        const long long e0 = (blk - d.work0) * T2V_ADAMW_BLOCK;
+        float a = 0.f;
+        if (e0 >= 0 && e0 < d.n) {
+            const long long left = d.n - e0;
+            const int cnt = left < T2V_ADAMW_BLOCK ? (int)left : T2V_ADAMW_BLOCK;
+            const float* g = d.grad + e0;
+            if (((uintptr_t)d.grad & 15) != 0) {
+#pragma unroll 1
+                for (int i = tid; i < cnt; i += 256) a += g[i] * g[i];
+            } else {
+                float4 G[Q];
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    const int i = (j * 256 + tid) * 4;
+                    if (i + 4 <= cnt) G[j] = *(const float4*)(g + i);
+                }
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    const int i = (j * 256 + tid) * 4;
+                    if (i + 4 <= cnt) {
+                        a += G[j].x * G[j].x; a += G[j].y * G[j].y; a += G[j].z * G[j].z; a += G[j].w * G[j].w;
+                    } else {
+#pragma unroll 1
+                        for (int e = i; e < cnt; ++e) a += g[e] * g[e];
+                    }
+                }
+            }
+        }
+        a = wave_sum(a);
+        if ((tid & 63) == 0) sh[tid >> 6] = a;
+        __syncthreads();
+        if (tid == 0) ws[blk] = (sh[0] + sh[1]) + (sh[2] + sh[3]);   // (0 for a work block that no tensor owns)
+        __syncthreads();   // sh is written again in the next round
+    }
+}
+// out[0] = sqrt(sum of the partials), summed in double in a fixed order (sumsq_final_kernel's); out[1] = the clip coefficient of
+// torch.nn.utils.clip_grad_norm_: min(1, max_norm / (norm + 1e-6)), a NaN norm giving a NaN coefficient as torch.clamp does.
+__global__ __launch_bounds__(256) void sumsq_multi_final_kernel(const float* __restrict__ ws, long long nblk, float max_norm, float* out) {
+    __shared__ double sh[256];
+    double a = 0.0;
+#pragma unroll 8
+    for (long long i = threadIdx.x; i < nblk; i += 256) a += (double)ws[i];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(sh[0]);
+        float coef = 1.0f;
+        if (max_norm > 0.f) {
+            coef = max_norm / (norm + 1e-6f);
+            if (coef > 1.0f) coef = 1.0f;   // (a NaN stays)
+        }
+        out[0] = norm;
+        out[1] = coef;
+    }
+}
+__global__ __launch_bounds__(256) void scale_multi_kernel(const t2v_adamw_tensor* __restrict__ table, int nt, long long nblocks,
+                                                          const float* __restrict__ coef_dev) {
+    constexpr int Q = T2V_ADAMW_BLOCK / (256 * 4);
+    const float c = *coef_dev;
+    if (c == 1.0f) return;   // nothing to clip: g * 1.0f is g, bit for bit, and the gradients are not touched
+    const int tid = threadIdx.x;
+    for (long long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const t2v_adamw_tensor d = table[owner_of(table, nt, blk)];
+        const long long e0 = (blk - d.work0) * T2V_ADAMW_BLOCK;
+        if (e0 < 0 || e0 >= d.n) continue;
+        const long long left = d.n - e0;
+        const int cnt = left < T2V_ADAMW_BLOCK ? (int)left : T2V_ADAMW_BLOCK;
+        float* g = d.grad + e0;
+        if (((uintptr_t)d.grad & 15) != 0) {
+#pragma unroll 1
+            for (int i = tid; i < cnt; i += 256) g[i] = g[i] * c;
+            continue;
+        }
+        float4 G[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int i = (j * 256 + tid) * 4;
+            if (i + 4 <= cnt) G[j] = *(const float4*)(g + i);
+        }
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int i = (j * 256 + tid) * 4;
+            if (i + 4 <= cnt) {
+                *(float4*)(g + i) = make_float4(G[j].x * c, G[j].y * c, G[j].z * c, G[j].w * c);
+            } else {
+#pragma unroll 1
+                for (int e = i; e < cnt; ++e) g[e] = g[e] * c;
+            }
+        }
+    }
+}
+// persistent grid, sized as blocks8 is: 8 workgroups per CU of a 256-CU part; fewer when there is less work
+inline unsigned blocks_multi(long long nblocks) { return (unsigned)(nblocks < 2048 ? nblocks : 2048); }
+}  // namespace
+
+extern "C" int t2v_adamw_multi(const t2v_adamw_tensor* table, int n_tensors, long long n_blocks, const t2v_adamw_hyper* hyper,
+                               int n_hyper, float grad_scale, const float* grad_scale_dev, void* stream) {
+    T2V_REQUIRE(table && hyper && n_tensors > 0 && n_blocks >= n_tensors && n_hyper >= 1 && n_hyper <= T2V_ADAMW_MAX_HYPER, T2V_EINVAL,
+                "t2v_adamw_multi");
+    T2V_REQUIRE((uintptr_t)table % 8 == 0, T2V_ESHAPE, "t2v_adamw_multi: the table must be 8-byte aligned");
+    AdamwRows rows;
+    for (int i = 0; i < T2V_ADAMW_MAX_HYPER; ++i) {
+        const t2v_adamw_hyper& h = hyper[i < n_hyper ? i : 0];
+        T2V_REQUIRE(h.step >= 1, T2V_EINVAL, "t2v_adamw_multi: step < 1");
+        const float bc1 = 1.0f - powf(h.beta1, (float)h.step), bc2 = 1.0f - powf(h.beta2, (float)h.step);
+        rows.lr[i] = h.lr; rows.wd[i] = h.weight_decay; rows.b1[i] = h.beta1; rows.b2[i] = h.beta2; rows.eps[i] = h.eps;
+        rows.bc1[i] = bc1; rows.bc2_sqrt[i] = sqrtf(bc2);
+    }
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks_multi(n_blocks)), dim3(256), 0, (hipStream_t)stream, table, n_tensors, n_blocks,
+                       rows, n_hyper, grad_scale, grad_scale_dev);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+extern "C" int t2v_sumsq_multi(const t2v_adamw_tensor* table, int n_tensors, long long n_blocks, float* ws, float max_norm, float* out,
+                               void* stream) {
+    T2V_REQUIRE(table && ws && out && n_tensors > 0 && n_blocks >= n_tensors, T2V_EINVAL, "t2v_sumsq_multi");
+    T2V_REQUIRE((uintptr_t)table % 8 == 0, T2V_ESHAPE, "t2v_sumsq_multi: the table must be 8-byte aligned");
+    hipLaunchKernelGGL(sumsq_multi_kernel, dim3(blocks_multi(n_blocks)), dim3(256), 0, (hipStream_t)stream, table, n_tensors, n_blocks, ws);
+    T2V_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sumsq_multi_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, n_blocks, max_norm, out);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+extern "C" int t2v_scale_multi(const t2v_adamw_tensor* table, int n_tensors, long long n_blocks, const float* coef_dev, void* stream) {
+    T2V_REQUIRE(table && coef_dev && n_tensors > 0 && n_blocks >= n_tensors, T2V_EINVAL, "t2v_scale_multi");
+    T2V_REQUIRE((uintptr_t)table % 8 == 0, T2V_ESHAPE, "t2v_scale_multi: the table must be 8-byte aligned");
+    hipLaunchKernelGGL(scale_multi_kernel, dim3(blocks_multi(n_blocks)), dim3(256), 0, (hipStream_t)stream, table, n_tensors, n_blocks,
+                       coef_dev);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
 // ---- library state ---------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
 void t2v_set_error(const char* msg) {

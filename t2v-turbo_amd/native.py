@@ -69,6 +69,22 @@ class EmaTensor(C.Structure):
                 ("reserved", C.c_int)]
 
 
+ADAMW_BLOCK = 4096       # T2V_ADAMW_BLOCK
+ADAMW_MAX_HYPER = 16     # T2V_ADAMW_MAX_HYPER
+
+
+class AdamwTensor(C.Structure):
+    """struct t2v_adamw_tensor, field for field (56 bytes)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_longlong),
+                ("work0", C.c_longlong), ("hyper", C.c_int), ("reserved", C.c_int)]
+
+
+class AdamwHyper(C.Structure):
+    """struct t2v_adamw_hyper, field for field (24 bytes)."""
+    _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("step", C.c_int)]
+
+
 class GemmDesc(C.Structure):
     """struct t2v_gemm_desc"""
     _fields_ = [
@@ -263,6 +279,9 @@ _SIGS = {
     "t2v_adamw8_step": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
                                   C.c_void_p]),
+    "t2v_adamw_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "t2v_sumsq_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "t2v_scale_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "t2v_quant8_blockwise": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2v_dequant8_blockwise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "t2v_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
@@ -886,6 +905,28 @@ class HipOps:
         ``EmaTensor`` records, ordered by ``work0``) in one launch (include/t2v_hip.h)."""
         assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(EmaTensor)
         self._call("t2v_ema_multi", _p(table), n_tensors, n_blocks, rate)
+
+    def adamw_multi(self, table, n_tensors, n_blocks, hyper, grad_scale=1.0, grad_scale_dev=None):
+        """fp32 AdamW over every tensor of ``table`` (a uint8 device tensor holding ``n_tensors`` ``AdamwTensor`` records, ordered by
+        ``work0``) in one launch.  ``hyper``: the rows ``(lr, weight_decay, beta1, beta2, eps, step)`` the records' ``hyper`` fields
+        index — host values, passed by value; ``grad_scale_dev``: a one-element fp32 device tensor multiplied into ``grad_scale``."""
+        assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(AdamwTensor)
+        assert grad_scale_dev is None or (grad_scale_dev.dtype == torch.float32 and grad_scale_dev.numel() == 1)
+        rows = hyper if isinstance(hyper, C.Array) else (AdamwHyper * len(hyper))(*[AdamwHyper(*h) for h in hyper])
+        self._call("t2v_adamw_multi", _p(table), n_tensors, n_blocks, C.cast(rows, C.c_void_p), len(rows), grad_scale, _p(grad_scale_dev))
+
+    def sumsq_multi(self, table, n_tensors, n_blocks, ws, max_norm, out):
+        """out[0] = the 2-norm of every gradient of ``table``, out[1] = min(1, max_norm / (out[0] + 1e-6)) (1 with max_norm <= 0);
+        ``ws``: ``n_blocks`` floats of workspace.  Deterministic."""
+        assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(AdamwTensor)
+        assert ws.dtype == torch.float32 and ws.numel() >= n_blocks and out.dtype == torch.float32 and out.numel() >= 2
+        self._call("t2v_sumsq_multi", _p(table), n_tensors, n_blocks, _p(ws), max_norm, _p(out))
+
+    def scale_multi(self, table, n_tensors, n_blocks, coef_dev):
+        """grad *= coef_dev[0] over every tensor of ``table``; a coefficient of exactly 1 leaves the gradients untouched."""
+        assert table.dtype == torch.uint8 and table.numel() >= n_tensors * C.sizeof(AdamwTensor)
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() >= 1
+        self._call("t2v_scale_multi", _p(table), n_tensors, n_blocks, _p(coef_dev))
 
     def sumsq(self, x, ws, out):
         self._call("t2v_sumsq", _p(x), x.numel(), _p(ws), _p(out))

@@ -6,7 +6,11 @@ step is one fused HIP kernel (``t2v_adamw_step``) instead of bitsandbytes' CUDA-
 
 ``AdamW8bit`` (below ``FlatAdamW``) is the ``torch.optim.Optimizer`` the reference's ``--use_8bit_adam`` asks for
 (``bnb.optim.AdamW8bit``): parameters and gradients stay where the trainer put them, the two moments are stored block-wise in
-8 bits (``t2v_adamw8_step``, one launch for every tensor).  ``compat.install()`` serves it as ``bitsandbytes.optim.AdamW8bit``."""
+8 bits (``t2v_adamw8_step``, one launch for every tensor).  ``compat.install()`` serves it as ``bitsandbytes.optim.AdamW8bit``.
+
+``AdamW`` (at the end) is its fp32 counterpart, the trainers' default without that flag: ``torch.optim.AdamW``'s constructor, state and
+checkpoints, one ``t2v_adamw_multi`` launch per step.  ``clip_grad_norm_`` / ``grad_clip_coef`` are the gradient clipping in front of it
+(``t2v_sumsq_multi``, ``t2v_scale_multi``): the norm and the coefficient stay on the device."""
 import operator
 
 import numpy as np
@@ -257,6 +261,23 @@ def dequantize_blockwise(codes, absmax, code, n):
     return (code[codes[:nb * QBLOCK].long()].view(nb, QBLOCK) * absmax[:nb, None]).reshape(-1)[:n]
 
 
+def adamw_definition(pf, grad, m, v, lr, betas, eps, wd, step, scale):
+    """One AdamW step on flat fp32 tensors in the kernels' operation order, every product and sum rounded separately (the device
+    kernels are compiled without fused multiply-adds so that both agree bit for bit on the moments): ``pf`` is updated in place from
+    the fresh moments, which are returned ``(m, v)``.  The scalars are formed in fp32 as t2v_adamw8_step / t2v_adamw_multi form them."""
+    f32 = np.float32
+    b1, b2, lr, wd, eps, scale = f32(betas[0]), f32(betas[1]), f32(lr), f32(wd), f32(eps), f32(scale)
+    bc1 = f32(1) - np.power(b1, f32(step), dtype=f32)
+    bc2_sqrt = np.sqrt(f32(1) - np.power(b2, f32(step), dtype=f32), dtype=f32)
+    decay, step_size = f32(1) - lr * wd, lr / bc1
+    gr = grad * float(scale)
+    pf.mul_(float(decay))
+    m = m * float(b1) + gr * float(f32(1) - b1)
+    v = v * float(b2) + (gr * float(f32(1) - b2)) * gr
+    pf.sub_((m * float(step_size)) / (v.sqrt() / float(bc2_sqrt) + float(eps)))
+    return m, v
+
+
 _TABLE_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state_block", "<i8"), ("n", "<i8"), ("work0", "<i8"),
                          ("lr", "<f4"), ("weight_decay", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])   # struct t2v_adamw8_tensor
 
@@ -403,24 +424,14 @@ class AdamW8bit(torch.optim.Optimizer):
         """The definition, vectorised over one tensor: dequantise, AdamW in fp32 with every product and sum rounded separately
         (the device kernel is compiled without fused multiply-adds so that both agree bit for bit on the moments), update the
         parameter from the fresh moments, re-quantise block by block."""
-        f32 = np.float32
         st, (is8, _, _) = self.state[p], self._layout[p]
         n, step = p.numel(), st["step"]
-        b1, b2, lr, wd, eps, scale = f32(betas[0]), f32(betas[1]), f32(lr), f32(wd), f32(eps), f32(scale)
-        bc1 = f32(1) - np.power(b1, f32(step), dtype=f32)
-        bc2_sqrt = np.sqrt(f32(1) - np.power(b2, f32(step), dtype=f32), dtype=f32)
-        decay, step_size = f32(1) - lr * wd, lr / bc1
         if is8:
             m = dequantize_blockwise(st["state1"], st["absmax1"], self.code1, n)
             v = dequantize_blockwise(st["state2"], st["absmax2"], self.code2, n)
         else:
             m, v = st["state1"], st["state2"]
-        gr = p.grad.reshape(-1) * float(scale)
-        pf = p.view(-1)
-        pf.mul_(float(decay))
-        m = m * float(b1) + gr * float(f32(1) - b1)
-        v = v * float(b2) + (gr * float(f32(1) - b2)) * gr
-        pf.sub_((m * float(step_size)) / (v.sqrt() / float(bc2_sqrt) + float(eps)))
+        m, v = adamw_definition(p.view(-1), p.grad.reshape(-1), m, v, lr, betas, eps, wd, step, scale)
         if is8:
             for key, amk, x, code in (("state1", "absmax1", m, self.code1), ("state2", "absmax2", v, self.code2)):
                 codes, absmax = quantize_blockwise(x, code)
@@ -502,3 +513,269 @@ class AdamW8bit(torch.optim.Optimizer):
             st["step"] = int(s["step"])
             for k in ("state1", "state2") + (("absmax1", "absmax2") if is8 else ()):
                 st[k].copy_(s[k].to(st[k].dtype))
+
+
+# ------------------------------------------------------------------------------------------------ fp32 AdamW and clipping, in place
+_ADAMW_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i8"), ("work0", "<i8"),
+                         ("hyper", "<i4"), ("reserved", "<i4")])   # struct t2v_adamw_tensor
+MAX_HYPER = 16   # T2V_ADAMW_MAX_HYPER
+
+
+def _ptrs(tensors):
+    return np.fromiter(map(_T.data_ptr, tensors), dtype=np.uint64, count=len(tensors))
+
+
+def adamw_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, rows=None):
+    """The ``t2v_adamw_tensor`` records of the tensors, in order -> (numpy record array, launches).  ``rows``: the hyper row of every
+    tensor, non-decreasing (None: all 0).  A launch takes at most ``MAX_HYPER`` distinct rows: ``launches`` is a list of
+    ``(first record, end record, work blocks, first row, rows)``; ``work0`` counts from the launch's first record and ``hyper`` from
+    its first row.  Gradients only (``t2v_sumsq_multi`` / ``t2v_scale_multi`` read nothing else): leave the other lists out."""
+    from .native import ADAMW_BLOCK
+    n = len(grads)
+    host = np.zeros(n, dtype=_ADAMW_DTYPE)
+    host["grad"] = _ptrs(grads)
+    for field, lst in (("param", params), ("exp_avg", exp_avgs), ("exp_avg_sq", exp_avg_sqs)):
+        if lst is not None:
+            host[field] = _ptrs(lst)
+    numel = np.fromiter(map(_T.numel, grads), dtype=np.int64, count=n)
+    blocks = (numel + ADAMW_BLOCK - 1) // ADAMW_BLOCK
+    rows = np.zeros(n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+    assert n > 0 and bool((numel > 0).all()) and bool((rows[1:] >= rows[:-1]).all())
+    host["n"] = numel
+    launches, start = [], 0
+    while start < n:
+        end = int(np.searchsorted(rows, rows[start] + MAX_HYPER, side="left"))
+        host["work0"][start:end] = np.cumsum(blocks[start:end]) - blocks[start:end]
+        host["hyper"][start:end] = rows[start:end] - rows[start]
+        launches.append((start, end, int(blocks[start:end].sum()), int(rows[start]), int(rows[end - 1] - rows[start]) + 1))
+        start = end
+    return host, launches
+
+
+def _upload(host, dev):
+    """A record array -> uint8 tensor on ``dev``; to a GPU through pinned memory, so that the host never waits for the copy.  Returns
+    (device tensor, what has to stay alive while the copy may still be reading it)."""
+    src = torch.from_numpy(host.view(np.uint8))
+    if dev.type != "cuda":
+        return src.clone(), None
+    pinned = src.pin_memory()
+    table = torch.empty(host.nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        table.copy_(pinned, non_blocking=True)
+    return table, pinned
+
+
+def _check_dense_f32(what, tensors, dev):
+    for t in tensors:
+        if t.is_sparse or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: parameters and gradients must be dense contiguous fp32 tensors on one device")
+
+
+class AdamW(torch.optim.Optimizer):
+    """``torch.optim.AdamW`` — its constructor, its per-parameter state (``step`` a 0-d fp32 CPU tensor, ``exp_avg``, ``exp_avg_sq``),
+    its checkpoints in both directions — whose step on the GPU is ONE ``t2v_adamw_multi`` launch over a device table of every tensor
+    that has a gradient, parameters, gradients and moments left where they are (one launch per 16 distinct ``(group, step)`` rows).
+    The table is uploaded again only when one of its pointers moves; the learning rates travel with the launch.  ``foreach`` and
+    ``fused`` are accepted and ignored; ``amsgrad`` / ``maximize`` / ``capturable`` / ``differentiable`` at their defaults only.  CPU
+    tensors run the same arithmetic in torch (``adamw_definition``), one tensor at a time.
+
+    ``step(grad_scale=...)`` multiplies the gradients first, without writing them: a float, or a one-element fp32 tensor on the
+    parameters' device — the coefficient of ``grad_clip_coef``, which then never visits the host."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        if amsgrad or maximize or capturable or differentiable:
+            raise NotImplementedError("AdamW: amsgrad / maximize / capturable / differentiable are accepted at their defaults only")
+        if torch.is_tensor(lr) and lr.numel() != 1:
+            raise ValueError("AdamW: a tensor lr must have one element")
+        if float(lr) < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("AdamW: invalid lr / betas / eps / weight_decay")
+        self._plan = None            # cached descriptor table of the device path
+        self.table_uploads = 0       # how often a table went to the device (test hook)
+        self.native_ops = None       # a HipOps to run the kernel with; None: the process-wide one for GPU tensors, torch on CPU tensors
+        super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      maximize=False, foreach=foreach, capturable=False, differentiable=False, fused=fused,
+                                      decoupled_weight_decay=True))
+
+    def add_param_group(self, param_group):
+        if any(param_group.get(k) for k in ("amsgrad", "maximize", "capturable", "differentiable")):
+            raise NotImplementedError("AdamW: amsgrad / maximize / capturable / differentiable are accepted at their defaults only")
+        super().add_param_group(param_group)
+        self._plan = None
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._plan = None
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """This class's own checkpoints and ``torch.optim.AdamW``'s (any of its foreach / fused forms: a ``step`` saved on a device comes
+        to the host here, once)."""
+        if any(g.get(k) for g in state_dict["param_groups"] for k in ("amsgrad", "maximize", "capturable", "differentiable")):
+            raise NotImplementedError("AdamW.load_state_dict: amsgrad / maximize / capturable / differentiable checkpoints")
+        super().load_state_dict(state_dict)
+        for s in self.state.values():
+            if "step" in s:
+                step = s["step"]
+                s["step"] = step.detach().to("cpu", torch.float32).reshape(()) if torch.is_tensor(step) else torch.tensor(float(step))
+        self._plan = None
+
+    @staticmethod
+    def _new_state(p, s):
+        s["step"] = torch.tensor(0.0, dtype=torch.float32)
+        s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0):
+        """One AdamW step over every parameter that has a gradient (only their ``step`` advances).  ``param_groups[i]["lr"]`` is read
+        now, so a scheduler may drive it."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        active = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not active:
+            return loss
+        dev = active[0].device
+        if dev.type != "cuda" and self.native_ops is None:
+            self._step_torch(float(grad_scale))
+            return loss
+        grads = [p.grad for p in active]
+        states = list(map(self.state.__getitem__, active))
+        if not all(states):   # the first gradient of a parameter
+            _check_dense_f32("AdamW", active, dev)
+            for p, s in zip(active, states):
+                if not s:
+                    self._new_state(p, s)
+        ms, vs = [s["exp_avg"] for s in states], [s["exp_avg_sq"] for s in states]
+        key = tuple(tuple(map(_T.data_ptr, lst)) for lst in (active, grads, ms, vs))
+        plan = self._plan
+        if plan is None or plan["key"] != key or float(plan["steps"][0]) != plan["first_step"] + plan["uses"]:
+            plan = self._plan = self._make_plan(active, grads, states, ms, vs, key, dev)
+        plan["steps"].add_(1.0)   # every state[p]["step"] of this plan is a 0-d view of this one buffer
+        plan["uses"] += 1
+        groups = self.param_groups
+        rows = [(float(groups[gi]["lr"]), groups[gi]["weight_decay"], groups[gi]["betas"][0], groups[gi]["betas"][1], groups[gi]["eps"],
+                 step0 + plan["uses"]) for gi, step0 in plan["rows"]]
+        scale, scale_dev = (1.0, grad_scale.detach()) if torch.is_tensor(grad_scale) else (float(grad_scale), None)
+        if scale_dev is not None and (scale_dev.device != dev or scale_dev.dtype != torch.float32 or scale_dev.numel() != 1):
+            raise ValueError("AdamW.step: a tensor grad_scale must be one fp32 element on the parameters' device")
+        ops = self.native_ops if self.native_ops is not None else _shared_ops()
+        import contextlib
+        from .native import AdamwHyper
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            for start, end, work, row0, n_rows in plan["launches"]:
+                hyper = (AdamwHyper * n_rows)(*[AdamwHyper(*r) for r in rows[row0:row0 + n_rows]])
+                ops.adamw_multi(plan["table"][start * _ADAMW_DTYPE.itemsize:], end - start, work, hyper, scale, scale_dev)
+        # The kernel writes the parameters behind torch's back: move every updated parameter's version counter — no launch — so that
+        # engine.params_fingerprint changes whichever module a parameter belongs to and the native engines re-pack their weights.
+        torch.autograd.graph.increment_version(active)
+        return loss
+
+    def _make_plan(self, active, grads, states, ms, vs, key, dev):
+        """Sort the tensors by hyper row — one row per (group, step) among them — and put the descriptor table on the device."""
+        _check_dense_f32("AdamW", active, dev)
+        _check_dense_f32("AdamW", grads, dev)
+        _check_dense_f32("AdamW", ms, dev)
+        _check_dense_f32("AdamW", vs, dev)
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        # The step counts of the plan's tensors move into ONE fp32 CPU buffer and every state[p]["step"] becomes a 0-d view of it (still
+        # torch's layout: a 0-d fp32 CPU tensor per parameter): a step then advances all of them with one add instead of one per tensor.
+        steps = [int(s["step"]) for s in states]
+        step_buf = torch.tensor(steps, dtype=torch.float32)
+        for i, s in enumerate(states):
+            s["step"] = step_buf[i]
+        row_keys = [(group_of[id(p)], st) for p, st in zip(active, steps)]
+        uniq = sorted(set(row_keys))
+        index = {k: i for i, k in enumerate(uniq)}
+        order = sorted(range(len(active)), key=lambda i: index[row_keys[i]])   # stable: parameters keep their order inside a row
+        pick = lambda lst: [lst[i] for i in order]   # noqa: E731
+        host, launches = adamw_table(pick(grads), pick(active), pick(ms), pick(vs), [index[row_keys[i]] for i in order])
+        table, pinned = _upload(host, dev)
+        self.table_uploads += 1
+        return dict(key=key, table=table, pinned=pinned, launches=launches, rows=uniq, steps=step_buf, first_step=steps[0], uses=0)
+
+    def _step_torch(self, grad_scale):
+        """The definition in torch, one tensor at a time, in the kernel's operation order."""
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                _check_dense_f32("AdamW", (p, p.grad), p.device)
+                s = self.state[p]
+                if not s:
+                    self._new_state(p, s)
+                s["step"] += 1
+                m, v = adamw_definition(p.view(-1), p.grad.reshape(-1), s["exp_avg"].view(-1), s["exp_avg_sq"].view(-1), float(g["lr"]),
+                                        g["betas"], g["eps"], g["weight_decay"], int(s["step"]), grad_scale)
+                s["exp_avg"].view(-1).copy_(m)
+                s["exp_avg_sq"].view(-1).copy_(v)
+
+
+_CLIP_PLANS = {}      # key -> cached device table and workspace (the few most recently used)
+_CLIP_PLANS_MAX = 4
+
+
+def _clip_plan(parameters):
+    """The plan of one norm launch over the gradients of ``parameters`` -> (plan, parameter list); plan None: this call is torch's
+    (a gradient that is not a dense contiguous fp32 CUDA tensor, more than one device, or no gradient at all)."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads or not all(map(_is_cuda, grads)):
+        return None, params
+    key = (tuple(map(_T.data_ptr, grads)), tuple(map(_T.numel, grads)), tuple(map(_dtype_of, grads)), tuple(map(_T.is_contiguous, grads)))
+    plan = _CLIP_PLANS.pop(key, None)
+    if plan is None:
+        dev = grads[0].device
+        if any(g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or g.numel() == 0 for g in grads):
+            return None, params
+        host, launches = adamw_table(grads)
+        (_, n, work, _, _), = launches
+        table, pinned = _upload(host, dev)
+        plan = dict(table=table, pinned=pinned, n=n, work=work, dev=dev, ws=torch.empty(work, dtype=torch.float32, device=dev))
+    _CLIP_PLANS[key] = plan                      # most recently used last
+    while len(_CLIP_PLANS) > _CLIP_PLANS_MAX:
+        _CLIP_PLANS.pop(next(iter(_CLIP_PLANS)))
+    return plan, params
+
+
+def _norm_and_coef(plan, max_norm):
+    out = torch.empty(2, dtype=torch.float32, device=plan["dev"])   # a buffer of its own: what is returned outlives the next call
+    with torch.cuda.device(plan["dev"]):
+        _shared_ops().sumsq_multi(plan["table"], plan["n"], plan["work"], plan["ws"], float(max_norm), out)
+    return out
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_``.  When every gradient present is a dense contiguous fp32 tensor on one GPU and ``norm_type``
+    is 2: one ``t2v_sumsq_multi`` (the norm and the coefficient min(1, max_norm / (norm + 1e-6)), left on the device) and one
+    ``t2v_scale_multi`` over a cached table of the gradients, no host synchronisation.  Any other call is torch's function, whole.
+    Returns the total norm, a 0-d fp32 tensor on the gradients' device."""
+    plan, params = _clip_plan(parameters) if float(norm_type) == 2.0 else (None, parameters)
+    if plan is None:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    out = _norm_and_coef(plan, max_norm)
+    if error_if_nonfinite and not bool(torch.isfinite(out[0])):   # (the one read of the norm)
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    with torch.cuda.device(plan["dev"]):
+        _shared_ops().scale_multi(plan["table"], plan["n"], plan["work"], out[1:])
+    return out[0]
+
+
+@torch.no_grad()
+def grad_clip_coef(parameters, max_norm):
+    """(total norm, clip coefficient) of the gradients of ``parameters``: two 0-d views of one device buffer, nothing scaled.
+    ``AdamW.step(grad_scale=coef)`` then clips inside the optimizer pass, and the scaled gradients are never written.  Gradients that
+    ``clip_grad_norm_`` would hand to torch get torch's norm and the same coefficient expression."""
+    plan, params = _clip_plan(parameters)
+    if plan is not None:
+        out = _norm_and_coef(plan, max_norm)
+        return out[0], out[1]
+    grads = [p.grad for p in params if p.grad is not None]
+    norm = torch.nn.utils.get_total_norm(grads, 2.0) if grads else torch.tensor(0.0)
+    out = torch.stack([norm.float(), torch.clamp(max_norm / (norm.float() + 1e-6), max=1.0)])
+    return out[0], out[1]
