@@ -308,18 +308,21 @@ int t2v_group_norm(const void* x0, int c0, int ld0, const void* x1, int c1, int 
 
 /* GroupNorm(+SiLU) whose statistics pass reads the column statistics the producing t2v_gemm launches wrote
  * (t2v_gemm_desc::colstat_out) instead of the tensor: cs0 [rows/32][c0][2] for x0, cs1 [rows/32][c1][2] for the second part of
- * a virtual concat (NULL without one); rows_per_unit % 32 == 0.  Two launches; ws: t2v_group_norm_cs_ws_floats(...) floats.
+ * a virtual concat (NULL without one, required with c1 > 0); rows_per_unit % 32 == 0, cs0 / cs1 8-byte aligned, ldo >= c0 + c1 (all
+ * checked: T2V_ESHAPE).  Two launches; ws: t2v_group_norm_cs_ws_floats(...) floats.
  * Same result as t2v_group_norm up to the summation order of the statistics (fixed: deterministic).  The statistics launch has two
  * forms, chosen by shape: one block per (group, unit) that leaves the per-channel affine (rstd gamma, beta - mean rstd gamma) in ws and
- * an apply pass that streams with it (even channels per group, c0 even, cs0 / cs1 16-byte aligned, 2 (c0 + c1) <= the ws floats per
- * unit, at most 32 slabs per thread), or per-slab-block partial sums that every block of the apply pass finishes for itself. */
+ * an apply pass that streams with it (even channels per group, at most 512 of them — 1 024 threads per block above 256 —, c0 even,
+ * cs0 / cs1 16-byte aligned, 2 (c0 + c1) <= the ws floats per unit, at most 32 slabs per thread, and not fewer than 16 channels per
+ * group where the statistics exceed 8 MB), or per-slab-block partial sums that every block of the apply pass finishes for itself. */
 long long t2v_group_norm_cs_ws_floats(int n_units, int rows_per_unit, int groups);
 int t2v_group_norm_cs(const float* cs0, const float* cs1, const void* x0, int c0, int ld0, const void* x1, int c1, int ld1,
                       int n_units, int rows_per_unit, int groups, float eps, const float* gamma, const float* beta, int silu,
                       float* ws, void* out, int ldo, const void* prefetch, long long prefetch_bytes, void* stream);
 /* (mean, rstd) per (unit, group) — the `stats` of t2v_gn_stats — from the column statistics alone: the training engine keeps them
  * for the GroupNorm backward and normalises with t2v_gn_apply (openaimodel3d.py:223-254 under autograd).  cs1 / c1: second part of
- * a virtual concat (NULL / 0: none).  ws: t2v_group_norm_cs_ws_floats floats. */
+ * a virtual concat (NULL / 0: none).  ws: t2v_group_norm_cs_ws_floats floats.  rows_per_unit % 32 == 0, c0 + c1 <= 4096 and a
+ * multiple of groups, cs0 / cs1 8-byte aligned (T2V_ESHAPE otherwise); the same two statistics forms as t2v_group_norm_cs. */
 int t2v_gn_stats_cs(const float* cs0, int c0, const float* cs1, int c1, int n_units, int rows_per_unit, int groups, float eps,
                     float* ws, float* stats, void* stream);
 
@@ -646,7 +649,9 @@ typedef struct t2v_wgrad_problem {
 int t2v_wgrad_tn_group(const t2v_wgrad_problem* problems, int n, float* ws, long long ws_bytes, void* stream);
 /* t2v_gn_coef_cs: the per-channel affine of a GroupNorm alone, from the producers' column statistics (t2v_gemm_desc::colstat_out layout,
  * one array per part of a virtual concat): coef fp32 [n_units][2][c0 + c1] — for consumers that normalise in their own load phase
- * (t2v_gemm_desc::gn_coef).  t2v_gn_coef_cs_supported: 1 / 0 (else t2v_group_norm_cs, which writes the normalised tensor). */
+ * (t2v_gemm_desc::gn_coef).  t2v_gn_coef_cs_supported: 1 where the direct statistics form of t2v_group_norm_cs takes the shape and the
+ * pointers (up to 512 channels per group), 0 otherwise (else t2v_group_norm_cs, which writes the normalised tensor); t2v_gn_coef_cs
+ * refuses a shape whose answer is 0 with T2V_ESHAPE. */
 int t2v_gn_coef_cs_supported(const float* cs0, int c0, const float* cs1, int c1, int n_units, int rows_per_unit, int groups);
 int t2v_gn_coef_cs(const float* cs0, int c0, const float* cs1, int c1, int n_units, int rows_per_unit, int groups, float eps,
                    const float* gamma, const float* beta, float* coef, void* stream);

@@ -1032,7 +1032,8 @@ static int gn_csd_threads(int c0, int c1, int groups, int slabs_per_unit, int n_
     if (!direct_on || cpg % 2 || c0 % 2 || ncp < 1 || ncp > 256 || (uintptr_t)cs0 % 16 || (cs1 && (uintptr_t)cs1 % 16)) return 0;
     if (ncp < 8 && (long long)n_units * slabs_per_unit * C * 8 > (8LL << 20)) return 0;
     const int lanes256 = 256 / ncp;
-    const int nt = (slabs_per_unit + lanes256 - 1) / lanes256 > 8 ? 1024 : 256;
+    // (the first cpg threads of a block write the group's coefficients: more than 256 channels per group need the 1 024-thread block)
+    const int nt = cpg > 256 || (slabs_per_unit + lanes256 - 1) / lanes256 > 8 ? 1024 : 256;
     return (slabs_per_unit + nt / ncp - 1) / (nt / ncp) <= GN_CSD_LOADS ? nt : 0;
 }
 static void gn_csd_launch(int nt, const float* cs0, int c0, const float* cs1, int c1, int n_units, int slabs_per_unit, int groups, float inv_count,
@@ -1055,6 +1056,7 @@ extern "C" int t2v_group_norm_cs(const float* cs0, const float* cs1, const void*
     if (rc) return rc;
     T2V_REQUIRE(ws && gamma && beta && out && ldo % 8 == 0 && cs0, T2V_EINVAL, "t2v_group_norm_cs: bad argument");
     if (!x1) { c1 = 0; ld1 = 0; }
+    T2V_REQUIRE(ldo >= c0 + c1, T2V_ESHAPE, "t2v_group_norm_cs: ldo smaller than the channel count");
     T2V_REQUIRE(rows_per_unit % 32 == 0 && (c1 == 0 || cs1) && GN_CS_BLOCKS <= gn_fuse_slabs(groups), T2V_ESHAPE,
                 "t2v_group_norm_cs: rows_per_unit must be a multiple of the 32-row statistics slab");
     T2V_REQUIRE((uintptr_t)cs0 % 8 == 0 && (!cs1 || (uintptr_t)cs1 % 8 == 0), T2V_ESHAPE, "t2v_group_norm_cs: unaligned statistics");
