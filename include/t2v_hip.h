@@ -755,6 +755,68 @@ int t2v_transpose_pad_bf16(const void* in, int ld_in, int rows, int cols, void* 
 int t2v_dropout_bf16(const void* x, int ldx, const void* resid, int ldr, void* out, int ldo, long long rows, int ncols, float p,
                      const void* seed, unsigned site, void* stream);
 
+/* ---------------------------------------------------------------- consistency head of the v2 step (csrc/train.hip)
+ * What train_latent_t2v_turbo_v2.py computes between the student's forward and its backward when no reward model is used, on
+ * activations laid out [B][per_clip] (contiguous; per_clip = C * F * H * W of the latent), in three launches and a small finishing
+ * one.  Per clip b with solver index i = index[b]:
+ *   t_s = ddim_timesteps[i], t_e = max(t_s - topk, 0)                                   (:996-1000)
+ *   alpha(t) = sqrt(alphas_cumprod[t]), sigma(t) = sqrt(1 - alphas_cumprod[t]), a_prev = ddim_alpha_cumprods_prev[i]
+ *   c_skip(t) = 0.25 / (s^2 + 0.25), c_out(t) = s / sqrt(s^2 + 0.25), s = timestep_scaling * t
+ *                                                        (scalings_for_boundary_conditions with sigma_data = 0.5, :1003-1015)
+ * The kernels look every per-clip coefficient up themselves: the host runs no B-row op and never synchronises.  The device cannot
+ * validate index without such a synchronisation: table reads are CLAMPED (index to [0, n_ddim), timesteps to [0, n_train)), so no
+ * value reads out of bounds; the Python layer validates index while it is still a CPU tensor.  Coefficients are formed in double and
+ * rounded to fp32 once; an element then takes two or three fp32 fused multiply-adds.
+ *
+ * t2v_cd_solver_step (no gradient; replaces :1169-1233 with use_scale = False, which the script asserts at :714):
+ *   x0  = x0c + w (x0c - x0u),   x0c = (z - sigma(t_s) c) / alpha(t_s),   x0u likewise with u
+ *   eps = c + w (c - u) - motion_gs * sqrt(1 - alpha_m) * score
+ *         alpha_m = alpha(t_s) where use_motion_guide[b] != 0 and i >= motion_min_index, else 1; no such term when score is NULL.
+ *         (1 - alpha)^0.5 is taken with alpha = sqrt(alphas_cumprod), as the script writes it (:1215-1226).
+ *   x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev) eps, rounded to nearest even into dt_out.
+ *   z_t, cond, uncond, score: one dtype code dt_in (T2V_F32 / T2V_BF16 / T2V_F16); w, motion_gs: fp32 [B]; use_motion_guide: bytes [B].
+ *
+ * t2v_cd_loss_fwd (replaces :1056-1065, :1246-1260):
+ *   model_pred = c_skip(t_s) z      + c_out(t_s) (z      - sigma(t_s) noise_pred)        / alpha(t_s)      -> model_pred (fp32)
+ *   target     = c_skip(t_e) x_prev + c_out(t_e) (x_prev - sigma(t_e) target_noise_pred) / alpha(t_e)
+ *   d = model_pred - target;  loss = mean over the N = B * per_clip elements of sqrt(d^2 + huber_c^2) - huber_c  (T2V_CD_HUBER)
+ *                                                                              or of d^2                         (T2V_CD_L2)
+ *   u = d loss / d model_pred = d / (N sqrt(d^2 + huber_c^2))  or  2 d / N                                       -> u (fp32)
+ *   noise_pred, target_noise_pred: fp32 or bf16 (a code each); z_t, x_prev: any of the three codes (x_prev as the solver step stored it).
+ *   The sum is taken in a fixed order: one partial per workgroup (T2V_CD_WG_ELEMS elements of one clip) in ws, then one launch of one
+ *   workgroup adds the partials in double.  Same inputs, same bits.  ws_floats >= t2v_cd_loss_ws_floats(B, per_clip).
+ *
+ * t2v_cd_loss_bwd (the autograd nodes of the above):
+ *   d_noise_pred = k_b (g_loss u + g_model_pred),   k_b = -c_out(t_s) sigma(t_s) / alpha(t_s)
+ *   g_loss: device scalar, NULL = 1.  g_model_pred: fp32, NULL = 0 (non-NULL when a reward branch sent a gradient into model_pred).
+ *   d_noise_pred: fp32 or bf16.
+ *
+ * Every entry point refuses before any launch: null pointers, non-positive sizes, an unknown loss type: T2V_EINVAL; a dtype code
+ * outside the above, a workspace that is too small, B > T2V_CD_MAX_CLIPS (a clip is one row of the launch grid): T2V_ESHAPE.
+ * 16-byte accesses when every activation pointer is 16-byte aligned (a clip that starts off a 16-byte boundary has a scalar head and
+ * tail); scalar accesses otherwise. */
+#define T2V_CD_WG_ELEMS 2048
+#define T2V_CD_MAX_CLIPS 65535
+#define T2V_CD_HUBER 0
+#define T2V_CD_L2 1
+typedef struct t2v_cd_sched {
+    const float* alphas_cumprod;           /* [n_train] fp32, device                                   */
+    const long long* ddim_timesteps;       /* [n_ddim] int64, device (DDIMSolver.ddim_timesteps)       */
+    const float* ddim_alpha_cumprods_prev; /* [n_ddim] fp32, device                                    */
+    const long long* index;                /* [B] int64, device: the solver index of every clip        */
+    int n_train, n_ddim, topk;
+    float timestep_scaling;
+} t2v_cd_sched;
+int t2v_cd_solver_step(const t2v_cd_sched* s, const void* z_t, const void* cond, const void* uncond, const void* score, int dt_in,
+                       const float* w, const float* motion_gs, const unsigned char* use_motion_guide, int motion_min_index, void* x_prev,
+                       int dt_out, int B, long long per_clip, void* stream);
+long long t2v_cd_loss_ws_floats(int B, long long per_clip);
+int t2v_cd_loss_fwd(const t2v_cd_sched* s, const void* noise_pred, int dt_np, const void* target_noise_pred, int dt_tnp, const void* z_t,
+                    int dt_z, const void* x_prev, int dt_xp, int loss_type, float huber_c, float* model_pred, float* u, float* ws,
+                    long long ws_floats, float* loss, int B, long long per_clip, void* stream);
+int t2v_cd_loss_bwd(const t2v_cd_sched* s, const float* u, const float* g_loss, const float* g_model_pred, void* d_noise_pred, int dt_out,
+                    int B, long long per_clip, void* stream);
+
 /* ---------------------------------------------------------------- recorded launch lists
  * The reference has no counterpart: its hot path is issued op by op from Python (and that is what bounds a small-batch step on
  * the host).  The engines of this library record a forward / backward once and replay it; t2v_replay walks such a recording —

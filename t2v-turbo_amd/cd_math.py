@@ -1,7 +1,8 @@
 """Consistency-distillation tensor math of the trainers (reference ``utils/common_utils.py:47-133,
 302-319`` and ``ode_solver/ddim_solver.py``): boundary scalings, x0/eps conversions, guidance
-embedding, pseudo-Huber loss, EMA update and the teacher DDIM solver.  Plain torch: these sit on the
-autograd path of training (the no-grad sampling step has its fused HIP kernel in scheduler.py)."""
+embedding, pseudo-Huber loss, EMA update and the teacher DDIM solver.  Plain torch: the definition the
+v1 step runs on and the v2 step's native consistency head (cd_head.py, csrc/train.hip) is tested against
+(the no-grad sampling step has its fused HIP kernel in scheduler.py)."""
 import numpy as np
 import torch
 

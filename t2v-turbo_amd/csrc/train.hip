@@ -198,3 +198,324 @@ extern "C" int t2v_transpose_pad_bf16(const void* in, int ld_in, int rows, int c
     T2V_CHECK_LAUNCH();
     return T2V_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The consistency head of the v2 step (train_latent_t2v_turbo_v2.py:996-1015, 1056-1065, 1169-1260; include/t2v_hip.h): the DDIM solver
+// step on the recorded teacher outputs, the boundary-scaled predictions with the pseudo-Huber / L2 loss, and the loss's gradient at
+// noise_pred — three launches (+ one small finishing launch of the loss sum) in place of the chain of ATen elementwise launches and
+// their autograd nodes.  Plain streams: a workgroup owns T2V_CD_WG_ELEMS consecutive elements of ONE clip (blockIdx.y), every thread
+// one run of 8.  The per-clip coefficients come from the device tables in the prologue of every thread, in double (a handful of
+// square roots against a launch that is latency-bound anyway), folded so that an element takes two or three fused multiply-adds;
+// table reads are clamped, so no value of index[] reads out of bounds.  16-byte accesses where every base is 16-byte aligned: a
+// clip that starts off such a boundary has a scalar head (and tail), handled by the first threads of its first workgroup; bases
+// that are not aligned make every run scalar.  Explicit fmaf throughout: the host simulator then rounds where the device does.
+namespace {
+
+__device__ __forceinline__ float cd_h2f(uint16_t bits) { _Float16 h; memcpy(&h, &bits, 2); return (float)h; }
+__device__ __forceinline__ uint16_t cd_f2h(float v) { const _Float16 h = (_Float16)v; uint16_t b; memcpy(&b, &h, 2); return b; }   // round to nearest even
+__device__ __forceinline__ int cd_esize(int dt) { return dt == T2V_F32 ? 4 : 2; }
+__device__ __forceinline__ float cd_ld1(const void* p, int dt, long long i) {
+    if (dt == T2V_F32) return ((const float*)p)[i];
+    const uint16_t b = ((const uint16_t*)p)[i];
+    return dt == T2V_BF16 ? bf2f(b) : cd_h2f(b);
+}
+__device__ __forceinline__ void cd_st1(void* p, int dt, long long i, float v) {
+    if (dt == T2V_F32) ((float*)p)[i] = v;
+    else ((uint16_t*)p)[i] = dt == T2V_BF16 ? f2bf(v) : cd_f2h(v);
+}
+// n <= 8 elements from element i on; vec: n == 8 and the address is 16-byte aligned
+__device__ __forceinline__ void cd_ld(const void* p, int dt, long long i, int n, bool vec, float* f) {
+    if (!vec) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = e < n ? cd_ld1(p, dt, i + e) : 0.f;
+        return;
+    }
+    if (dt == T2V_F32) {
+        const uint4 a = *(const uint4*)((const float*)p + i), b = *(const uint4*)((const float*)p + i + 4);
+        f[0] = __uint_as_float(a.x); f[1] = __uint_as_float(a.y); f[2] = __uint_as_float(a.z); f[3] = __uint_as_float(a.w);
+        f[4] = __uint_as_float(b.x); f[5] = __uint_as_float(b.y); f[6] = __uint_as_float(b.z); f[7] = __uint_as_float(b.w);
+        return;
+    }
+    const uint4 a = *(const uint4*)((const uint16_t*)p + i);
+    if (dt == T2V_BF16) {
+        unpack8(a, f);
+    } else {
+        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { f[2 * e] = cd_h2f((uint16_t)(w[e] & 0xffffu)); f[2 * e + 1] = cd_h2f((uint16_t)(w[e] >> 16)); }
+    }
+}
+__device__ __forceinline__ void cd_st(void* p, int dt, long long i, int n, bool vec, const float* f) {
+    if (!vec) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (e < n) cd_st1(p, dt, i + e, f[e]);
+        return;
+    }
+    if (dt == T2V_F32) {
+        *(uint4*)((float*)p + i) = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
+        *(uint4*)((float*)p + i + 4) = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]), __float_as_uint(f[6]), __float_as_uint(f[7]));
+        return;
+    }
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const uint32_t lo = dt == T2V_BF16 ? f2bf(f[2 * e]) : cd_f2h(f[2 * e]), hi = dt == T2V_BF16 ? f2bf(f[2 * e + 1]) : cd_f2h(f[2 * e + 1]);
+        w[e] = lo | (hi << 16);
+    }
+    *(uint4*)((uint16_t*)p + i) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The runs of a thread: run 0 is its 8-element vector (if any), run 1 a single head / tail element (first workgroup of the clip only).
+struct CdRuns {
+    long long e0[2];
+    int n[2];
+    bool vec;
+};
+__device__ __forceinline__ CdRuns cd_runs(long long clip0, long long per_clip, int aligned) {
+    CdRuns r;
+    long long head = aligned ? (8 - (clip0 & 7)) & 7 : 0;   // elements in front of the clip's first 16-byte boundary
+    if (head > per_clip) head = per_clip;
+    const long long nvec = (per_clip - head) >> 3, tail0 = head + 8 * nvec;
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    r.vec = aligned != 0;
+    r.e0[0] = head + 8 * v;
+    r.n[0] = v < nvec ? 8 : 0;
+    r.e0[1] = 0;
+    r.n[1] = 0;
+    if (blockIdx.x == 0) {
+        const long long t = threadIdx.x;
+        if (t < head) { r.e0[1] = t; r.n[1] = 1; }
+        else if (t - head < per_clip - tail0) { r.e0[1] = tail0 + (t - head); r.n[1] = 1; }
+    }
+    return r;
+}
+
+// schedule values of clip b: alpha = sqrt(alphas_cumprod[t]), sigma = sqrt(1 - alphas_cumprod[t]) at t_s and t_e, every read clamped
+struct CdClip {
+    int i;
+    long long ts, te;
+    double a_s, s_s, a_e, s_e;
+};
+__device__ __forceinline__ CdClip cd_clip(const t2v_cd_sched& s, int b) {
+    CdClip c;
+    long long i = s.index[b];
+    i = i < 0 ? 0 : (i > s.n_ddim - 1 ? s.n_ddim - 1 : i);
+    long long ts = s.ddim_timesteps[i];
+    ts = ts < 0 ? 0 : (ts > s.n_train - 1 ? s.n_train - 1 : ts);
+    long long te = ts - s.topk;
+    te = te < 0 ? 0 : te;
+    c.i = (int)i; c.ts = ts; c.te = te;
+    const double acs = (double)s.alphas_cumprod[ts], ace = (double)s.alphas_cumprod[te];
+    c.a_s = sqrt(acs); c.s_s = sqrt(1.0 - acs);
+    c.a_e = sqrt(ace); c.s_e = sqrt(1.0 - ace);
+    return c;
+}
+// model_pred = c_skip x + c_out (x - sigma eps) / alpha = P x + Q eps   (scalings_for_boundary_conditions, sigma_data = 0.5)
+__device__ __forceinline__ void cd_boundary(double scaling, long long t, double alpha, double sigma, float& P, float& Q) {
+    const double sc = scaling * (double)t, den = sc * sc + 0.25;
+    const double c_skip = 0.25 / den, c_out = sc / sqrt(den);
+    P = (float)(c_skip + c_out / alpha);
+    Q = (float)(-c_out * sigma / alpha);
+}
+
+__global__ __launch_bounds__(256) void cd_solver_step_kernel(const t2v_cd_sched s, const void* __restrict__ z_t, const void* __restrict__ cond,
+                                                             const void* __restrict__ uncond, const void* __restrict__ score, int dt_in,
+                                                             const float* __restrict__ w, const float* __restrict__ motion_gs,
+                                                             const unsigned char* __restrict__ use_motion_guide, int motion_min_index,
+                                                             void* __restrict__ x_prev, int dt_out, long long per_clip, int aligned) {
+    const int b = blockIdx.y;
+    const long long clip0 = (long long)b * per_clip;
+    const CdRuns r = cd_runs(clip0, per_clip, aligned);
+    if (r.n[0] == 0 && r.n[1] == 0) return;
+    const CdClip c = cd_clip(s, b);
+    // x_prev = sqrt(a_prev) (z - sigma g) / alpha + sqrt(1 - a_prev) (g - m score),   g = c + w (c - u)
+    const double ap = (double)s.ddim_alpha_cumprods_prev[c.i], sap = sqrt(ap), s1ap = sqrt(1.0 - ap);
+    const float A = (float)(sap / c.a_s), Bg = (float)(s1ap - sap * c.s_s / c.a_s), wb = w[b];
+    float Cm = 0.f;
+    if (score && use_motion_guide[b] && c.i >= motion_min_index) Cm = (float)(s1ap * (double)motion_gs[b] * sqrt(1.0 - c.a_s));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int n = r.n[k];
+        if (n == 0) continue;
+        const long long e = clip0 + r.e0[k];
+        const bool vec = r.vec && n == 8;
+        float z[8], cc[8], uu[8], sc[8], o[8];
+        cd_ld(z_t, dt_in, e, n, vec, z);
+        cd_ld(cond, dt_in, e, n, vec, cc);
+        cd_ld(uncond, dt_in, e, n, vec, uu);
+        if (score) cd_ld(score, dt_in, e, n, vec, sc);
+        else
+            for (int j = 0; j < 8; ++j) sc[j] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {   // (all 8 lanes of the run: the ones past n hold zeros and are not stored)
+            const float g = fmaf(wb, cc[j] - uu[j], cc[j]);
+            float v = fmaf(A, z[j], Bg * g);
+            if (score) v = fmaf(-Cm, sc[j], v);
+            o[j] = v;
+        }
+        cd_st(x_prev, dt_out, e, n, vec, o);
+    }
+}
+
+__global__ __launch_bounds__(256) void cd_loss_fwd_kernel(const t2v_cd_sched s, const void* __restrict__ noise_pred, int dt_np,
+                                                          const void* __restrict__ target_noise_pred, int dt_tnp, const void* __restrict__ z_t,
+                                                          int dt_z, const void* __restrict__ x_prev, int dt_xp, int loss_type, float huber_c,
+                                                          float inv_n, float* __restrict__ model_pred, float* __restrict__ u,
+                                                          float* __restrict__ ws, long long per_clip, int aligned) {
+    __shared__ float sh[4];
+    const int b = blockIdx.y;
+    const long long clip0 = (long long)b * per_clip;
+    const CdRuns r = cd_runs(clip0, per_clip, aligned);
+    float acc = 0.f;
+    if (r.n[0] != 0 || r.n[1] != 0) {
+        const CdClip c = cd_clip(s, b);
+        float Ps, Qs, Pe, Qe;
+        cd_boundary((double)s.timestep_scaling, c.ts, c.a_s, c.s_s, Ps, Qs);
+        cd_boundary((double)s.timestep_scaling, c.te, c.a_e, c.s_e, Pe, Qe);
+        const float c2 = huber_c * huber_c;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int n = r.n[k];
+            if (n == 0) continue;
+            const long long e = clip0 + r.e0[k];
+            const bool vec = r.vec && n == 8;
+            float np[8], tn[8], z[8], xp[8], mp[8], uo[8];
+            cd_ld(noise_pred, dt_np, e, n, vec, np);
+            cd_ld(target_noise_pred, dt_tnp, e, n, vec, tn);
+            cd_ld(z_t, dt_z, e, n, vec, z);
+            cd_ld(x_prev, dt_xp, e, n, vec, xp);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                mp[j] = fmaf(Ps, z[j], Qs * np[j]);
+                const float d = mp[j] - fmaf(Pe, xp[j], Qe * tn[j]);
+                if (loss_type == T2V_CD_HUBER) {
+                    const float q = sqrtf(fmaf(d, d, c2));
+                    acc += j < n ? q - huber_c : 0.f;
+                    uo[j] = (d * inv_n) / q;
+                } else {
+                    acc += j < n ? d * d : 0.f;
+                    uo[j] = 2.0f * d * inv_n;
+                }
+            }
+            cd_st(model_pred, T2V_F32, e, n, vec, mp);
+            cd_st(u, T2V_F32, e, n, vec, uo);
+        }
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[(long long)b * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ __launch_bounds__(256) void cd_loss_final_kernel(const float* __restrict__ ws, long long n_partials, double inv_count,
+                                                            float* __restrict__ loss) {
+    __shared__ double sh[256];
+    double a = 0.0;
+    for (long long i = threadIdx.x; i < n_partials; i += 256) a += (double)ws[i];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(sh[0] * inv_count);
+}
+
+__global__ __launch_bounds__(256) void cd_loss_bwd_kernel(const t2v_cd_sched s, const float* __restrict__ u, const float* __restrict__ g_loss,
+                                                          const float* __restrict__ g_model_pred, void* __restrict__ d_noise_pred, int dt_out,
+                                                          long long per_clip, int aligned) {
+    const int b = blockIdx.y;
+    const long long clip0 = (long long)b * per_clip;
+    const CdRuns r = cd_runs(clip0, per_clip, aligned);
+    if (r.n[0] == 0 && r.n[1] == 0) return;
+    const CdClip c = cd_clip(s, b);
+    float Ps, Qs;
+    cd_boundary((double)s.timestep_scaling, c.ts, c.a_s, c.s_s, Ps, Qs);   // d model_pred / d noise_pred = Q(t_s) = -c_out sigma / alpha
+    const float gl = g_loss ? g_loss[0] : 1.0f;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int n = r.n[k];
+        if (n == 0) continue;
+        const long long e = clip0 + r.e0[k];
+        const bool vec = r.vec && n == 8;
+        float uu[8], gm[8], o[8];
+        cd_ld(u, T2V_F32, e, n, vec, uu);
+        if (g_model_pred) cd_ld(g_model_pred, T2V_F32, e, n, vec, gm);
+        else
+            for (int j = 0; j < 8; ++j) gm[j] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = Qs * (g_model_pred ? fmaf(gl, uu[j], gm[j]) : gl * uu[j]);
+        cd_st(d_noise_pred, dt_out, e, n, vec, o);
+    }
+}
+
+bool cd_dt_ok(int dt) { return dt == T2V_F32 || dt == T2V_BF16 || dt == T2V_F16; }
+bool cd_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+int cd_check_sched(const t2v_cd_sched* s, int B, long long per_clip, const char* what) {
+    T2V_REQUIRE(s && s->alphas_cumprod && s->ddim_timesteps && s->ddim_alpha_cumprods_prev && s->index, T2V_EINVAL, what);
+    T2V_REQUIRE(B > 0 && per_clip > 0 && s->n_train > 0 && s->n_ddim > 0 && s->topk >= 0, T2V_EINVAL, what);
+    T2V_REQUIRE(B <= T2V_CD_MAX_CLIPS, T2V_ESHAPE, "t2v_cd_*: more than T2V_CD_MAX_CLIPS clips");
+    T2V_REQUIRE((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS < (1ll << 31), T2V_ESHAPE, "t2v_cd_*: clip too long");
+    return T2V_OK;
+}
+
+}  // namespace
+
+extern "C" int t2v_cd_solver_step(const t2v_cd_sched* s, const void* z_t, const void* cond, const void* uncond, const void* score, int dt_in,
+                                  const float* w, const float* motion_gs, const unsigned char* use_motion_guide, int motion_min_index,
+                                  void* x_prev, int dt_out, int B, long long per_clip, void* stream) {
+    T2V_REQUIRE(z_t && cond && uncond && w && x_prev && (!score || (motion_gs && use_motion_guide)), T2V_EINVAL,
+                "t2v_cd_solver_step: null pointer");
+    const int rc = cd_check_sched(s, B, per_clip, "t2v_cd_solver_step: null schedule pointer / non-positive size");
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(cd_dt_ok(dt_in) && cd_dt_ok(dt_out), T2V_ESHAPE, "t2v_cd_solver_step: dtype codes are fp32, bf16 or fp16");
+    const int aligned = cd_al16(z_t) && cd_al16(cond) && cd_al16(uncond) && (!score || cd_al16(score)) && cd_al16(x_prev);
+    const dim3 grid((unsigned)((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS), (unsigned)B);
+    hipLaunchKernelGGL(cd_solver_step_kernel, grid, dim3(256), 0, (hipStream_t)stream, *s, z_t, cond, uncond, score, dt_in, w, motion_gs,
+                       use_motion_guide, motion_min_index, x_prev, dt_out, per_clip, aligned);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" long long t2v_cd_loss_ws_floats(int B, long long per_clip) {
+    if (B <= 0 || per_clip <= 0) return 0;
+    return (long long)B * ((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS);
+}
+
+extern "C" int t2v_cd_loss_fwd(const t2v_cd_sched* s, const void* noise_pred, int dt_np, const void* target_noise_pred, int dt_tnp,
+                               const void* z_t, int dt_z, const void* x_prev, int dt_xp, int loss_type, float huber_c, float* model_pred,
+                               float* u, float* ws, long long ws_floats, float* loss, int B, long long per_clip, void* stream) {
+    T2V_REQUIRE(noise_pred && target_noise_pred && z_t && x_prev && model_pred && u && ws && loss, T2V_EINVAL, "t2v_cd_loss_fwd: null pointer");
+    const int rc = cd_check_sched(s, B, per_clip, "t2v_cd_loss_fwd: null schedule pointer / non-positive size");
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(loss_type == T2V_CD_HUBER || loss_type == T2V_CD_L2, T2V_EINVAL, "t2v_cd_loss_fwd: unknown loss type");
+    T2V_REQUIRE((dt_np == T2V_F32 || dt_np == T2V_BF16) && (dt_tnp == T2V_F32 || dt_tnp == T2V_BF16), T2V_ESHAPE,
+                "t2v_cd_loss_fwd: noise_pred / target_noise_pred are fp32 or bf16");
+    T2V_REQUIRE(cd_dt_ok(dt_z) && cd_dt_ok(dt_xp), T2V_ESHAPE, "t2v_cd_loss_fwd: dtype codes are fp32, bf16 or fp16");
+    const long long partials = t2v_cd_loss_ws_floats(B, per_clip);
+    T2V_REQUIRE(ws_floats >= partials, T2V_ESHAPE, "t2v_cd_loss_fwd: workspace smaller than t2v_cd_loss_ws_floats");
+    const int aligned = cd_al16(noise_pred) && cd_al16(target_noise_pred) && cd_al16(z_t) && cd_al16(x_prev) && cd_al16(model_pred) && cd_al16(u);
+    const double count = (double)B * (double)per_clip;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(partials / B), (unsigned)B);
+    hipLaunchKernelGGL(cd_loss_fwd_kernel, grid, dim3(256), 0, st, *s, noise_pred, dt_np, target_noise_pred, dt_tnp, z_t, dt_z, x_prev, dt_xp,
+                       loss_type, huber_c, (float)(1.0 / count), model_pred, u, ws, per_clip, aligned);
+    T2V_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cd_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, partials, 1.0 / count, loss);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_cd_loss_bwd(const t2v_cd_sched* s, const float* u, const float* g_loss, const float* g_model_pred, void* d_noise_pred,
+                               int dt_out, int B, long long per_clip, void* stream) {
+    T2V_REQUIRE(u && d_noise_pred, T2V_EINVAL, "t2v_cd_loss_bwd: null pointer");
+    const int rc = cd_check_sched(s, B, per_clip, "t2v_cd_loss_bwd: null schedule pointer / non-positive size");
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(dt_out == T2V_F32 || dt_out == T2V_BF16, T2V_ESHAPE, "t2v_cd_loss_bwd: d_noise_pred is fp32 or bf16");
+    const int aligned = cd_al16(u) && (!g_model_pred || cd_al16(g_model_pred)) && cd_al16(d_noise_pred);
+    const dim3 grid((unsigned)((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS), (unsigned)B);
+    hipLaunchKernelGGL(cd_loss_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, *s, u, g_loss, g_model_pred, d_noise_pred, dt_out, per_clip,
+                       aligned);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}

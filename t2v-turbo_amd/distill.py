@@ -1,4 +1,4 @@
-"""One v1 consistency-distillation step (reference ``train_t2v_turbo_v1_lora.py:978-1196``, with the image-reward branch
+"""``distill_step``: one v1 consistency-distillation step (reference ``train_t2v_turbo_v1_lora.py:978-1196``, with the image-reward branch
 :1043-1063 when a ``reward_fn`` is given; the reward models themselves are out of scope and stay whatever the caller
 passes): student forward with grad, teacher cond + uncond forwards, CFG estimate, one DDIM
 solver step, target forward with the student's own weights, pseudo-Huber / L2 loss, backward, flat
@@ -17,7 +17,10 @@ Execution split on MI355X: the two frozen-teacher forwards run on the native inf
   gradients written straight into the ``grad_sync`` flat buffer; only the M = B-row conditioning branch (time / fps / guidance
   MLPs + ``emb_layers``) stays in torch autograd.
 
-The gradient exchange is the single flat all-reduce of ``dist.FlatGradSync``."""
+The gradient exchange is the single flat all-reduce of ``dist.FlatGradSync``.
+
+``distill_step_v2`` (below): one step of ``train_latent_t2v_turbo_v2.py`` — recorded teacher outputs, full fine-tuning student,
+optional EMA target network, the consistency head of ``cd_head`` between the student's forward and its backward."""
 import torch
 import torch.nn.functional as F
 
@@ -204,5 +207,154 @@ def distill_step(unet, teacher_unet, solver, noise_scheduler, latents, prompt_em
             if grad_sync is None:
                 optimizer.zero_grad(set_to_none=True)
         _mark("sync+clip+step")
+    info["host_ms"] = {b[0]: round((b[1] - a[1]) * 1e3, 2) for a, b in zip(_marks, _marks[1:])}
+    return loss, info
+
+
+def _reward_clips(rng, key, text, short_txt, bsz, n):
+    """Which clips a reward branch scores, and with which captions (train_latent_t2v_turbo_v2.py:1078-1097): ``n`` clips among those
+    with a short caption when any has one, else among all with the long captions."""
+    short_idx = torch.tensor([i for i, t in enumerate(short_txt or []) if t != ""], dtype=torch.long)
+    if len(short_idx) == 0:
+        b_idx = rng[key] if key in rng else torch.randperm(bsz)[:n]
+        return b_idx, None if text is None else [text[int(i)] for i in b_idx]
+    b_idx = rng[key] if key in rng else short_idx[torch.randperm(len(short_idx))[:min(len(short_idx), n)]]
+    return b_idx, [short_txt[int(i)] for i in b_idx]
+
+
+def _decode_frames(vae, model_pred, b_idx, idx, vae_scale_factor):
+    """A few frames of ``model_pred`` through the frozen VAE -> images in [0, 1] (:1100-1108)."""
+    sel = model_pred[b_idx][:, :, idx] / vae_scale_factor
+    sel = sel.permute(0, 2, 1, 3, 4)
+    sel = sel.reshape(len(b_idx) * len(idx), *sel.shape[2:])
+    decoded = vae.decode(sel.to(vae.dtype))
+    return (decoded / 2 + 0.5).clamp(0, 1)
+
+
+def distill_step_v2(unet, solver, noise_scheduler, batch, *, target_unet=None, optimizer=None, fps=16, topk=5, w_min=5.0, w_max=15.0,
+                    time_cond_proj_dim=256, motion_gs=0.05, percentage=0.5, use_motion_cond=False, num_ddim_timesteps=50,
+                    timestep_scaling_factor=10.0, loss_type="huber", huber_c=0.001, max_grad_norm=1.0, ema_decay=0.95, weight_dtype=None,
+                    device=None, rng=None, vae=None, vae_scale_factor=0.18215, reward_fn=None, reward_scale=0.0, reward_frame_bsz=2,
+                    reward_train_bsz=2, video_rm_fn=None, video_reward_scale=0.0, video_rm_frame_bsz=8, keep_noise_pred=False):
+    """One step of ``train_latent_t2v_turbo_v2.py:975-1276`` in the single-role case (one process computes every loss; the script's
+    split over ``vlcd_processes`` / ``reward_train_processes`` is launcher policy).  ``batch``: the dict ``latent_io`` yields —
+    ``index, z_t, cond_teacher_out, uncond_teacher_out, score, use_motion_guide, prompt_emb, txt[, short_txt]``.  In order: draw ``w``
+    and build the guidance / motion-guidance embeddings; student forward through the module call (the full fine-tuning route on the
+    GPU); ``cd_head.solver_step_v2`` on the recorded teacher outputs; target forward under ``no_grad`` (``target_unet`` when given,
+    else ``unet``); ``cd_head.consistency_loss``; the optional image-reward and video-reward branches on VAE-decoded frames of
+    ``model_pred`` (the reward callables are the caller's); ``backward``; clip + optimizer step (the clip coefficient stays on the
+    device where the optimizer takes it: ``optim.AdamW``); ``zero_grad``; ``update_ema`` of the target.
+
+    ``weight_dtype``: what the recorded activations are cast to (the script: bf16); None keeps the records' dtype.  ``rng`` may pin the
+    draws for tests: dict(w, reward_frames, reward_batch, video_start, video_batch).  Returns (loss, info)."""
+    from . import cd_head, optim
+    import time as _time
+    _marks = [("start", _time.perf_counter())]
+
+    def _mark(name):
+        _marks.append((name, _time.perf_counter()))
+
+    rng = rng or {}
+    index = batch["index"].long()
+    cd_head.check_index(index, num_ddim_timesteps)     # (a CPU tensor as it leaves the dataloader: refused here, not on the device)
+    assert solver.ddim_timesteps.numel() == num_ddim_timesteps and not getattr(solver, "use_scale", False)
+    dev = torch.device(device) if device is not None else next(unet.parameters()).device
+    pdt = next(unet.parameters()).dtype
+    bsz = index.shape[0]
+
+    def act(name):
+        t = batch[name].to(dev, non_blocking=True)
+        return t if weight_dtype is None else t.to(weight_dtype)
+
+    z_t, cond_out, uncond_out = act("z_t"), act("cond_teacher_out"), act("uncond_teacher_out")
+    score = act("score") if batch.get("score") is not None else None
+    text, short_txt = batch.get("txt"), batch.get("short_txt")
+    prompt_emb = batch["prompt_emb"].to(dev, non_blocking=True).to(pdt)
+    adt = z_t.dtype
+
+    # per-clip host values (B rows, on the host where index lives), then to the device through pinned memory
+    index_h, umg_h = index.cpu(), batch["use_motion_guide"].cpu().bool().reshape(bsz)
+    start_h = _on_device(solver.ddim_timesteps, torch.device("cpu"))[index_h]
+    end_h = torch.clamp(start_h - topk, min=0)
+    w = rng.get("w")
+    if w is None:
+        w = (w_max - w_min) * torch.rand((bsz,)) + w_min
+    w = w.cpu().float()
+    min_index = cd_head.motion_min_index(percentage, num_ddim_timesteps)
+    mgs_h = torch.where(torch.logical_and(umg_h, index_h >= (1 - percentage) * num_ddim_timesteps), torch.full((bsz,), float(motion_gs)),
+                        torch.zeros(bsz))
+    w_embedding = _to_device_async(cd_math.guidance_scale_embedding(w, embedding_dim=time_cond_proj_dim).to(pdt), dev)
+    mgs_embedding = _to_device_async(cd_math.guidance_scale_embedding(mgs_h, embedding_dim=time_cond_proj_dim).to(pdt), dev) \
+        if use_motion_cond else None
+    # (the script casts w and motion_gs to the activations' dtype before the CFG estimate: the same values, carried in fp32)
+    w_dev = _to_device_async(w.to(adt).float(), dev)
+    mgs_dev = _to_device_async(mgs_h.to(adt).float(), dev)
+    index_dev, umg_dev = _to_device_async(index_h, dev), _to_device_async(umg_h, dev)
+    start_timesteps, timesteps = _to_device_async(start_h, dev), _to_device_async(end_h, dev)
+    acp = noise_scheduler.alphas_cumprod
+    kw = dict(context=prompt_emb, fps=fps, timestep_cond=w_embedding)
+    if mgs_embedding is not None:
+        kw["motion_cond"] = mgs_embedding
+    _mark("inputs")
+
+    # 7. online (student) prediction, with grad
+    noise_pred = unet(z_t.to(pdt), start_timesteps, **kw)
+    if keep_noise_pred and noise_pred.requires_grad:
+        noise_pred.retain_grad()
+    _mark("student_fwd")
+
+    # 8. CFG estimate of the recorded teacher outputs + motion-prior guidance -> one DDIM solver step; 9. target prediction
+    with torch.no_grad():
+        x_prev = cd_head.solver_step_v2(solver, acp, index_dev, z_t, cond_out, uncond_out, score, w_dev, mgs_dev, umg_dev,
+                                        min_index=min_index, out_dtype=adt)
+        unet_fn = target_unet if target_unet is not None else unet
+        target_noise_pred = unet_fn(x_prev.to(next(unet_fn.parameters()).dtype), timesteps, **kw)
+    _mark("solver+target")
+
+    # 10. boundary scalings + loss
+    distill_loss, model_pred = cd_head.consistency_loss(solver, acp, index_dev, noise_pred, target_noise_pred, z_t, x_prev, topk=topk,
+                                                        timestep_scaling=timestep_scaling_factor, loss_type=loss_type, huber_c=huber_c)
+    loss = distill_loss
+    info = {"index": index_h, "start_timesteps": start_h, "timesteps": end_h, "distill_loss": distill_loss.detach(), "x_prev": x_prev}
+    n_frames = model_pred.shape[2]
+    if reward_fn is not None and reward_scale > 0:
+        assert vae is not None, "the reward branches decode through the VAE"
+        idx = rng["reward_frames"] if "reward_frames" in rng else torch.randperm(n_frames)[:reward_frame_bsz]
+        b_idx, selected_text = _reward_clips(rng, "reward_batch", text, short_txt, bsz, reward_train_bsz)
+        reward_loss = -reward_fn(_decode_frames(vae, model_pred, b_idx, idx, vae_scale_factor), selected_text).mean() * reward_scale
+        info["reward_loss"] = reward_loss.detach()
+        loss = loss + reward_loss.to(loss.dtype)
+    if video_rm_fn is not None and video_reward_scale > 0:
+        assert vae is not None, "the reward branches decode through the VAE"
+        assert n_frames > video_rm_frame_bsz, "the video reward model scores a strided subset of the frames"
+        skip_frames = n_frames // video_rm_frame_bsz
+        start_id = int(rng["video_start"]) if "video_start" in rng else int(torch.randint(0, skip_frames, (1,))[0])
+        idx = torch.arange(start_id, n_frames, skip_frames)[:video_rm_frame_bsz]
+        assert len(idx) == video_rm_frame_bsz
+        b_idx, selected_text = _reward_clips(rng, "video_batch", text, short_txt, bsz, 1)     # (video_rm_train_bsz == 1, :1115)
+        decoded = _decode_frames(vae, model_pred, b_idx, idx, vae_scale_factor)
+        decoded = decoded.reshape(len(b_idx), video_rm_frame_bsz, *decoded.shape[1:])
+        video_rm_loss = -video_rm_fn(decoded, selected_text).mean() * video_reward_scale
+        info["video_rm_loss"] = video_rm_loss.detach()
+        loss = loss + video_rm_loss.to(loss.dtype)
+    _mark("loss")
+
+    # 11. backward, clip, update; 12. EMA of the target
+    if optimizer is not None:
+        loss.backward()
+        _mark("backward")
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        if isinstance(optimizer, optim.AdamW):     # takes the clip coefficient as a device scalar: the scaled gradients are never written
+            info["grad_norm"], coef = optim.grad_clip_coef(params, max_grad_norm)
+            optimizer.step(grad_scale=coef)
+        else:
+            info["grad_norm"] = optim.clip_grad_norm_(params, max_grad_norm)
+            optimizer.step()
+        optimizer.zero_grad(set_to_none=True)
+        if target_unet is not None:
+            optim.update_ema(target_unet.parameters(), unet.parameters(), ema_decay)
+        _mark("clip+step+ema")
+    if keep_noise_pred:
+        info["noise_pred"], info["target_noise_pred"] = noise_pred, target_noise_pred     # (the seam tensors, for tests)
     info["host_ms"] = {b[0]: round((b[1] - a[1]) * 1e3, 2) for a, b in zip(_marks, _marks[1:])}
     return loss, info

@@ -38,6 +38,17 @@ class RankLossProblem(C.Structure):
     _fields_ = [("ref", C.c_void_p), ("gen", C.c_void_p), ("d_gen", C.c_void_p), ("rows", C.c_longlong)]
 
 
+CD_WG_ELEMS = 2048        # T2V_CD_WG_ELEMS
+CD_MAX_CLIPS = 65535      # T2V_CD_MAX_CLIPS
+CD_HUBER, CD_L2 = 0, 1    # T2V_CD_HUBER, T2V_CD_L2
+
+
+class CdSched(C.Structure):
+    """struct t2v_cd_sched, field for field (48 bytes)."""
+    _fields_ = [("alphas_cumprod", C.c_void_p), ("ddim_timesteps", C.c_void_p), ("ddim_alpha_cumprods_prev", C.c_void_p),
+                ("index", C.c_void_p), ("n_train", C.c_int), ("n_ddim", C.c_int), ("topk", C.c_int), ("timestep_scaling", C.c_float)]
+
+
 ROWLIN_MAX_ROWS = 8       # T2V_ROWLIN_MAX_ROWS
 ROWLIN_LDS_FLOATS = 16384  # t2v_rowlin_fwd: B * K of a problem (its input rows wait in LDS)
 
@@ -317,6 +328,13 @@ _SIGS = {
                                    C.c_void_p, C.c_uint, C.c_void_p]),
     "t2v_lcm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2v_cd_solver_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
+    "t2v_cd_loss_ws_floats": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "t2v_cd_loss_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong,
+                                  C.c_void_p]),
+    "t2v_cd_loss_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
 }
 # Entry points of a T2V_EXPERIMENTAL=1 build only (libt2v_hip_exp.so: the measured negative results — the second t2v_gemm kernel family, the
 # one-launch feed-forward): bound when the loaded library has them.
@@ -1026,6 +1044,63 @@ class HipOps:
         assert loss.numel() >= len(problems)
         self._call("t2v_rank_loss", C.cast(arr, C.c_void_p), len(problems), int(n), int(rank_k), float(alpha), _p(ws), ws.numel(), _p(loss),
                    keep=arr)
+
+    # ---- the consistency head of the v2 step (csrc/train.hip: t2v_cd_*) ----------------------------------------------------------------
+    @staticmethod
+    def cd_sched(alphas_cumprod, ddim_timesteps, ddim_alpha_cumprods_prev, index, topk, timestep_scaling):
+        """struct t2v_cd_sched over device tables: fp32 ``alphas_cumprod`` [n_train] and ``ddim_alpha_cumprods_prev`` [n_ddim], int64
+        ``ddim_timesteps`` [n_ddim] and ``index`` [B].  The struct holds raw pointers: the caller keeps the tensors alive."""
+        for t in (alphas_cumprod, ddim_alpha_cumprods_prev):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
+        for t in (ddim_timesteps, index):
+            assert t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1
+        assert ddim_timesteps.numel() == ddim_alpha_cumprods_prev.numel()
+        return CdSched(_p(alphas_cumprod), _p(ddim_timesteps), _p(ddim_alpha_cumprods_prev), _p(index), alphas_cumprod.numel(),
+                       ddim_timesteps.numel(), int(topk), float(timestep_scaling))
+
+    @staticmethod
+    def _cd_geometry(t, *same):
+        B = t.shape[0]
+        per_clip = t.numel() // max(B, 1)
+        for o in same:
+            assert o is None or (o.is_contiguous() and o.numel() == t.numel()), "t2v_cd_*: contiguous [B][per_clip] tensors of one size"
+        assert t.is_contiguous()
+        return B, per_clip
+
+    def cd_solver_step(self, sched, z_t, cond, uncond, score, w, motion_gs, use_motion_guide, motion_min_index, x_prev):
+        """x_prev (any of fp32 / bf16 / fp16, round to nearest even) = one DDIM step from the CFG estimate of the recorded teacher
+        outputs with the motion-prior guidance term (``score`` None: without it) — t2v_cd_solver_step, one launch."""
+        B, per_clip = self._cd_geometry(z_t, cond, uncond, score, x_prev)
+        assert all(t is None or t.dtype == z_t.dtype for t in (cond, uncond, score))
+        assert w.dtype == torch.float32 and w.numel() == B and w.is_contiguous()
+        if score is not None:
+            assert motion_gs.dtype == torch.float32 and motion_gs.numel() == B and motion_gs.is_contiguous()
+            assert use_motion_guide.dtype in (torch.bool, torch.uint8) and use_motion_guide.numel() == B and use_motion_guide.is_contiguous()
+        self._call("t2v_cd_solver_step", C.byref(sched), _p(z_t), _p(cond), _p(uncond), _p(score), _DT.get(z_t.dtype, -1), _p(w),
+                   _p(motion_gs) if score is not None else None, _p(use_motion_guide) if score is not None else None,
+                   int(motion_min_index), _p(x_prev), _DT.get(x_prev.dtype, -1), B, per_clip, keep=sched)
+
+    def cd_loss_ws_floats(self, B, per_clip):
+        return int(self.lib.t2v_cd_loss_ws_floats(int(B), int(per_clip)))
+
+    def cd_loss_fwd(self, sched, noise_pred, target_noise_pred, z_t, x_prev, loss_type, huber_c, model_pred, u, ws, loss):
+        """model_pred, u = d(loss)/d(model_pred) (both fp32) and the scalar ``loss`` — t2v_cd_loss_fwd: one elementwise launch with
+        per-workgroup partial sums in ``ws`` and one small finishing launch (fixed order: same inputs, same bits)."""
+        B, per_clip = self._cd_geometry(noise_pred, target_noise_pred, z_t, x_prev, model_pred, u)
+        assert model_pred.dtype == torch.float32 and u.dtype == torch.float32
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and loss.dtype == torch.float32 and loss.numel() >= 1
+        self._call("t2v_cd_loss_fwd", C.byref(sched), _p(noise_pred), _DT.get(noise_pred.dtype, -1), _p(target_noise_pred),
+                   _DT.get(target_noise_pred.dtype, -1), _p(z_t), _DT.get(z_t.dtype, -1), _p(x_prev), _DT.get(x_prev.dtype, -1),
+                   int(loss_type), float(huber_c), _p(model_pred), _p(u), _p(ws), ws.numel(), _p(loss), B, per_clip, keep=sched)
+
+    def cd_loss_bwd(self, sched, u, g_loss, g_model_pred, d_noise_pred):
+        """d_noise_pred (fp32 or bf16) = k_b (g_loss u + g_model_pred); ``g_loss`` a one-element fp32 device tensor or None (= 1),
+        ``g_model_pred`` fp32 or None — t2v_cd_loss_bwd, one launch."""
+        B, per_clip = self._cd_geometry(u, g_model_pred, d_noise_pred)
+        assert u.dtype == torch.float32 and (g_model_pred is None or g_model_pred.dtype == torch.float32)
+        assert g_loss is None or (g_loss.dtype == torch.float32 and g_loss.numel() == 1)
+        self._call("t2v_cd_loss_bwd", C.byref(sched), _p(u), _p(g_loss), _p(g_model_pred), _p(d_noise_pred),
+                   _DT.get(d_noise_pred.dtype, -1), B, per_clip, keep=sched)
 
     # ---- the B-row conditioning branch (csrc/full_grad.hip: t2v_rowlin_*) ----------------------------------------------------------
     # A problem is a dict of tensors and flags, the same for the three entries (see ``t2v_rowlin_problem``): x, w, bias, res, y (fwd: the
