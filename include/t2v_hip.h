@@ -817,6 +817,55 @@ int t2v_cd_loss_fwd(const t2v_cd_sched* s, const void* noise_pred, int dt_np, co
 int t2v_cd_loss_bwd(const t2v_cd_sched* s, const float* u, const float* g_loss, const float* g_model_pred, void* d_noise_pred, int dt_out,
                     int B, long long per_clip, void* stream);
 
+/* ---------------------------------------------------------------- producer of the v2 latent records (csrc/train.hip)
+ * What preprocess_scripts/preprocess_with_motion_prior.py:328-409 computes BETWEEN the teacher's forwards when it makes the records the
+ * v2 step trains on, on activations laid out [B][per_clip] as above, with the tables of t2v_cd_sched (topk and timestep_scaling are
+ * not read): one launch each, every per-clip coefficient looked up on the device, no host synchronisation.  Table reads are clamped
+ * as above; coefficients are formed in double and rounded to fp32 once; an element takes one product and one fused multiply-add.
+ *
+ * t2v_cd_add_noise (scheduler/t2v_turbo_scheduler.py:470-495 at t_s = ddim_timesteps[index[b]]):
+ *   z = sqrt(alphas_cumprod[t_s]) x + sqrt(1 - alphas_cumprod[t_s]) noise                                         -> z (fp32)
+ *   x, noise: a dtype code each (T2V_F32 / T2V_BF16 / T2V_F16).  z_lp: NULL, or a copy of z rounded to nearest even into dt_lp
+ *   (T2V_BF16 / T2V_F16): the UNet's input.
+ *
+ * t2v_ddim_reverse_step (ode_solver/ddim_solver.py ddim_reverse_step inside motion_prior_sample.py:27-37): inversion step i
+ * (0 <= i < n_ddim) of EVERY clip; the inverted latent x stays fp32, in place, between the steps.  Per clip b with
+ * idx = clamp(index[b]):
+ *   i >  idx: the clip's inversion is over: x is not written; x_lp (when given) is rewritten from it.
+ *   i == idx and prev != NULL: prev <- x first (z_example_prev; the original latent when idx == 0, :351-355), then the step.
+ *   i <= idx: t = ddim_timesteps[i], t_p = max(t - step_ratio, 0), a_n = alphas_cumprod[t], a = alphas_cumprod[t_p],
+ *             x <- (x - sqrt(1 - a) eps) sqrt(a_n / a) + sqrt(1 - a_n) eps;  x_lp (when given) <- x rounded to nearest even.
+ *   eps: fp32 or bf16 (the teacher's prediction at (x_lp, t)).  prev: fp32 or NULL.  x_lp: bf16 / fp16 or NULL.
+ *
+ * t2v_pack_f16_multi: up to T2V_PACK_MAX tensors converted into ONE fp16 buffer in one launch (the hand-over of a batch of records:
+ * one launch and then one copy to the host instead of a cast and a copy per tensor).  `table` is a HOST array, handed to the kernel by
+ * value; entry j holds `rows` rows of n contiguous elements and writes row r to dst[dst_off + r * dst_stride, ... + n) (rows = 1: one
+ * flat tensor; rows = B with dst_stride = the record length: one tensor of every clip into a clip-by-clip layout).  Entries must not
+ * overlap each other in dst (not checked).  The conversion is torch.Tensor.to(torch.float16): round to nearest even, overflow
+ * to +-inf, NaN stays NaN (the quiet NaN without a payload keeps its bits, 0x7E00), subnormals are produced, -0 is kept.  A workgroup moves T2V_PACK_BLOCK elements
+ * of one row; 16-byte accesses between the destination's first and last 16-byte boundary inside the row when the source is
+ * 16-byte aligned there, scalar accesses for the rest; nothing outside the rows' destination ranges is written.
+ *
+ * Refused before any launch: null pointers, non-positive sizes, a step outside [0, n_ddim), a negative step_ratio or offset, an entry
+ * count outside 1..T2V_PACK_MAX: T2V_EINVAL; a dtype code outside the above, B > T2V_CD_MAX_CLIPS, a source off its element boundary,
+ * an entry whose rows overlap (dst_stride < n) or that ends past dst_numel: T2V_ESHAPE. */
+#define T2V_PACK_MAX 16
+#define T2V_PACK_BLOCK 2048
+typedef struct t2v_pack_entry {
+    const void* src;      /* [rows][n] contiguous, device */
+    long long n;          /* elements of a row */
+    long long rows;
+    long long dst_off;    /* first element of row 0 in dst */
+    long long dst_stride; /* elements between the starts of two rows in dst (not read when rows == 1) */
+    int dt;               /* T2V_F32, T2V_BF16 or T2V_F16 */
+    int reserved;
+} t2v_pack_entry;
+int t2v_cd_add_noise(const t2v_cd_sched* s, const void* x, int dt_x, const void* noise, int dt_noise, float* z, void* z_lp, int dt_lp,
+                     int B, long long per_clip, void* stream);
+int t2v_ddim_reverse_step(const t2v_cd_sched* s, int i, int step_ratio, float* x, const void* eps, int dt_eps, float* prev, void* x_lp,
+                          int dt_lp, int B, long long per_clip, void* stream);
+int t2v_pack_f16_multi(const t2v_pack_entry* table /* host */, int n_entries, void* dst, long long dst_numel, void* stream);
+
 /* ---------------------------------------------------------------- recorded launch lists
  * The reference has no counterpart: its hot path is issued op by op from Python (and that is what bounds a small-batch step on
  * the host).  The engines of this library record a forward / backward once and replay it; t2v_replay walks such a recording —

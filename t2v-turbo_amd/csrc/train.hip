@@ -449,6 +449,118 @@ __global__ __launch_bounds__(256) void cd_loss_bwd_kernel(const t2v_cd_sched s, 
     }
 }
 
+// ---- the producer side of the v2 latent records (preprocess_with_motion_prior.py:328-409; include/t2v_hip.h) ----------------------------
+// The elementwise steps between the teacher's forwards when a record is made: the forward-diffusion sample, one DDIM inversion step of
+// every clip (the state stays fp32, in place; a clip whose inversion is over keeps its state), and the hand-over of a record's tensors
+// as ONE fp16 buffer.  Same streams, runs and coefficient rules as the consistency head above.
+__global__ __launch_bounds__(256) void cd_add_noise_kernel(const t2v_cd_sched s, const void* __restrict__ x, int dt_x,
+                                                           const void* __restrict__ noise, int dt_noise, float* __restrict__ z,
+                                                           void* __restrict__ z_lp, int dt_lp, long long per_clip, int aligned) {
+    const int b = blockIdx.y;
+    const long long clip0 = (long long)b * per_clip;
+    const CdRuns r = cd_runs(clip0, per_clip, aligned);
+    if (r.n[0] == 0 && r.n[1] == 0) return;
+    const CdClip c = cd_clip(s, b);
+    const float A = (float)c.a_s, S = (float)c.s_s;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int n = r.n[k];
+        if (n == 0) continue;
+        const long long e = clip0 + r.e0[k];
+        const bool vec = r.vec && n == 8;
+        float xx[8], nn[8], o[8];
+        cd_ld(x, dt_x, e, n, vec, xx);
+        cd_ld(noise, dt_noise, e, n, vec, nn);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = fmaf(A, xx[j], S * nn[j]);
+        cd_st(z, T2V_F32, e, n, vec, o);
+        if (z_lp) cd_st(z_lp, dt_lp, e, n, vec, o);
+    }
+}
+
+__global__ __launch_bounds__(256) void ddim_reverse_step_kernel(const t2v_cd_sched s, int i, int step_ratio, float* x,
+                                                                const void* __restrict__ eps, int dt_eps, float* __restrict__ prev,
+                                                                void* __restrict__ x_lp, int dt_lp, long long per_clip, int aligned) {
+    const int b = blockIdx.y;
+    const long long clip0 = (long long)b * per_clip;
+    const CdRuns r = cd_runs(clip0, per_clip, aligned);
+    if (r.n[0] == 0 && r.n[1] == 0) return;
+    long long idx = s.index[b];
+    idx = idx < 0 ? 0 : (idx > s.n_ddim - 1 ? s.n_ddim - 1 : idx);
+    const bool done = i > idx, save = prev != nullptr && i == idx;
+    if (done && !x_lp) return;
+    // x <- (x - sqrt(1 - a) eps) sqrt(a_n / a) + sqrt(1 - a_n) eps = P x + Q eps        (i < n_ddim: checked by the entry point)
+    float P = 1.f, Q = 0.f;
+    if (!done) {
+        long long t = s.ddim_timesteps[i];
+        t = t < 0 ? 0 : (t > s.n_train - 1 ? s.n_train - 1 : t);
+        long long tp = t - step_ratio;
+        tp = tp < 0 ? 0 : tp;
+        const double an = (double)s.alphas_cumprod[t], a = (double)s.alphas_cumprod[tp], ratio = sqrt(an / a);
+        P = (float)ratio;
+        Q = (float)(sqrt(1.0 - an) - sqrt(1.0 - a) * ratio);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int n = r.n[k];
+        if (n == 0) continue;
+        const long long e = clip0 + r.e0[k];
+        const bool vec = r.vec && n == 8;
+        float xx[8], ee[8];
+        cd_ld(x, T2V_F32, e, n, vec, xx);
+        if (save) cd_st(prev, T2V_F32, e, n, vec, xx);
+        if (!done) {
+            cd_ld(eps, dt_eps, e, n, vec, ee);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xx[j] = fmaf(P, xx[j], Q * ee[j]);
+            cd_st(x, T2V_F32, e, n, vec, xx);
+        }
+        if (x_lp) cd_st(x_lp, dt_lp, e, n, vec, xx);
+    }
+}
+
+// One workgroup per work block of T2V_PACK_BLOCK elements of ONE row of ONE entry (the last entry with work0 <= block; the table travels
+// by value).  A row's destination starts on a 2-byte boundary: the elements in front of its first 16-byte boundary and the ones behind
+// the last full run of 8 are moved one by one by the first lanes of the row's first work block; when the source is not 16-byte aligned
+// at that boundary every run is scalar.
+struct PackArgs {
+    t2v_pack_entry e[T2V_PACK_MAX];
+    long long work0[T2V_PACK_MAX];
+    int n;
+};
+__global__ __launch_bounds__(256) void pack_f16_multi_kernel(const PackArgs a, uint16_t* __restrict__ dst) {
+    const long long blk = blockIdx.x;
+    t2v_pack_entry d = a.e[0];
+    long long w0 = a.work0[0];
+#pragma unroll
+    for (int j = 1; j < T2V_PACK_MAX; ++j)
+        if (j < a.n && a.work0[j] <= blk) { d = a.e[j]; w0 = a.work0[j]; }
+    const long long per_row = (d.n + T2V_PACK_BLOCK - 1) / T2V_PACK_BLOCK;
+    const long long row = (blk - w0) / per_row, lb = (blk - w0) % per_row;
+    if (row >= d.rows) return;
+    const int es = cd_esize(d.dt);
+    const char* src = (const char*)d.src + row * d.n * es;
+    uint16_t* o = dst + d.dst_off + row * d.dst_stride;
+    long long head = (long long)(((16 - ((uintptr_t)o & 15)) & 15) >> 1);
+    if (head > d.n) head = d.n;
+    const bool vec = (((uintptr_t)src + (uintptr_t)(head * es)) & 15) == 0;
+    if (!vec) head = 0;
+    const long long nvec = (d.n - head) >> 3, tail0 = head + 8 * nvec;
+    const long long v = lb * 256 + threadIdx.x;
+    if (v < nvec) {
+        float f[8];
+        cd_ld(src, d.dt, head + 8 * v, 8, vec, f);
+        cd_st(o, T2V_F16, head + 8 * v, 8, vec, f);
+    }
+    if (lb == 0) {
+        const long long t = threadIdx.x;
+        long long e = -1;
+        if (t < head) e = t;
+        else if (t - head < d.n - tail0) e = tail0 + (t - head);
+        if (e >= 0) cd_st1(o, T2V_F16, e, cd_ld1(src, d.dt, e));
+    }
+}
+
 bool cd_dt_ok(int dt) { return dt == T2V_F32 || dt == T2V_BF16 || dt == T2V_F16; }
 bool cd_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 int cd_check_sched(const t2v_cd_sched* s, int B, long long per_clip, const char* what) {
@@ -516,6 +628,67 @@ extern "C" int t2v_cd_loss_bwd(const t2v_cd_sched* s, const float* u, const floa
     const dim3 grid((unsigned)((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS), (unsigned)B);
     hipLaunchKernelGGL(cd_loss_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, *s, u, g_loss, g_model_pred, d_noise_pred, dt_out, per_clip,
                        aligned);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_cd_add_noise(const t2v_cd_sched* s, const void* x, int dt_x, const void* noise, int dt_noise, float* z, void* z_lp,
+                                int dt_lp, int B, long long per_clip, void* stream) {
+    T2V_REQUIRE(x && noise && z, T2V_EINVAL, "t2v_cd_add_noise: null pointer");
+    const int rc = cd_check_sched(s, B, per_clip, "t2v_cd_add_noise: null schedule pointer / non-positive size");
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(cd_dt_ok(dt_x) && cd_dt_ok(dt_noise), T2V_ESHAPE, "t2v_cd_add_noise: x / noise are fp32, bf16 or fp16");
+    T2V_REQUIRE(!z_lp || dt_lp == T2V_BF16 || dt_lp == T2V_F16, T2V_ESHAPE, "t2v_cd_add_noise: the low-precision copy is bf16 or fp16");
+    const int aligned = cd_al16(x) && cd_al16(noise) && cd_al16(z) && cd_al16(z_lp);
+    const dim3 grid((unsigned)((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS), (unsigned)B);
+    hipLaunchKernelGGL(cd_add_noise_kernel, grid, dim3(256), 0, (hipStream_t)stream, *s, x, dt_x, noise, dt_noise, z, z_lp, dt_lp, per_clip,
+                       aligned);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_ddim_reverse_step(const t2v_cd_sched* s, int i, int step_ratio, float* x, const void* eps, int dt_eps, float* prev,
+                                     void* x_lp, int dt_lp, int B, long long per_clip, void* stream) {
+    T2V_REQUIRE(x && eps, T2V_EINVAL, "t2v_ddim_reverse_step: null pointer");
+    const int rc = cd_check_sched(s, B, per_clip, "t2v_ddim_reverse_step: null schedule pointer / non-positive size");
+    if (rc != T2V_OK) return rc;
+    T2V_REQUIRE(i >= 0 && i < s->n_ddim && step_ratio >= 0, T2V_EINVAL, "t2v_ddim_reverse_step: step outside the solver grid / negative step_ratio");
+    T2V_REQUIRE(dt_eps == T2V_F32 || dt_eps == T2V_BF16, T2V_ESHAPE, "t2v_ddim_reverse_step: eps is fp32 or bf16");
+    T2V_REQUIRE(!x_lp || dt_lp == T2V_BF16 || dt_lp == T2V_F16, T2V_ESHAPE, "t2v_ddim_reverse_step: the low-precision copy is bf16 or fp16");
+    const int aligned = cd_al16(x) && cd_al16(eps) && cd_al16(prev) && cd_al16(x_lp);
+    const dim3 grid((unsigned)((per_clip + T2V_CD_WG_ELEMS - 1) / T2V_CD_WG_ELEMS), (unsigned)B);
+    hipLaunchKernelGGL(ddim_reverse_step_kernel, grid, dim3(256), 0, (hipStream_t)stream, *s, i, step_ratio, x, eps, dt_eps, prev, x_lp, dt_lp,
+                       per_clip, aligned);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_pack_f16_multi(const t2v_pack_entry* table, int n_entries, void* dst, long long dst_numel, void* stream) {
+    T2V_REQUIRE(table && dst && n_entries > 0 && n_entries <= T2V_PACK_MAX && dst_numel > 0, T2V_EINVAL,
+                "t2v_pack_f16_multi: null pointer / entry count outside 1..T2V_PACK_MAX");
+    T2V_REQUIRE((uintptr_t)dst % 2 == 0, T2V_ESHAPE, "t2v_pack_f16_multi: the destination must be 2-byte aligned");
+    PackArgs a = {};
+    a.n = n_entries;
+    long long blocks = 0;
+    for (int j = 0; j < n_entries; ++j) {
+        const t2v_pack_entry& d = table[j];
+        T2V_REQUIRE(d.src && d.n > 0 && d.rows > 0 && d.dst_off >= 0, T2V_EINVAL,
+                    "t2v_pack_f16_multi: null source / non-positive size / negative offset");
+        T2V_REQUIRE(cd_dt_ok(d.dt), T2V_ESHAPE, "t2v_pack_f16_multi: dtype codes are fp32, bf16 or fp16");
+        T2V_REQUIRE((uintptr_t)d.src % (d.dt == T2V_F32 ? 4 : 2) == 0, T2V_ESHAPE, "t2v_pack_f16_multi: a source off its element boundary");
+        T2V_REQUIRE(d.rows == 1 || d.dst_stride >= d.n, T2V_ESHAPE, "t2v_pack_f16_multi: rows of one entry overlap in the destination");
+        // the last element the entry writes: dst_off + (rows - 1) * dst_stride + n - 1 < dst_numel, without overflow
+        T2V_REQUIRE(d.n <= dst_numel && d.dst_off <= dst_numel - d.n &&
+                        (d.rows == 1 || d.dst_stride <= (dst_numel - d.n - d.dst_off) / (d.rows - 1)),
+                    T2V_ESHAPE, "t2v_pack_f16_multi: an entry past the end of the destination");
+        T2V_REQUIRE(d.rows < (1ll << 31) && d.n < (1ll << 40), T2V_ESHAPE, "t2v_pack_f16_multi: too many elements for one launch");
+        a.e[j] = d;
+        a.work0[j] = blocks;
+        blocks += d.rows * ((d.n + T2V_PACK_BLOCK - 1) / T2V_PACK_BLOCK);
+        T2V_REQUIRE(blocks < (1ll << 31), T2V_ESHAPE, "t2v_pack_f16_multi: too many elements for one launch");
+    }
+    T2V_REQUIRE(blocks < (1ll << 31), T2V_ESHAPE, "t2v_pack_f16_multi: too many elements for one launch");
+    hipLaunchKernelGGL(pack_f16_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (uint16_t*)dst);
     T2V_CHECK_LAUNCH();
     return T2V_OK;
 }

@@ -49,6 +49,16 @@ class CdSched(C.Structure):
                 ("index", C.c_void_p), ("n_train", C.c_int), ("n_ddim", C.c_int), ("topk", C.c_int), ("timestep_scaling", C.c_float)]
 
 
+PACK_MAX = 16             # T2V_PACK_MAX
+PACK_BLOCK = 2048         # T2V_PACK_BLOCK
+
+
+class PackEntry(C.Structure):
+    """struct t2v_pack_entry, field for field (48 bytes)."""
+    _fields_ = [("src", C.c_void_p), ("n", C.c_longlong), ("rows", C.c_longlong), ("dst_off", C.c_longlong), ("dst_stride", C.c_longlong),
+                ("dt", C.c_int), ("reserved", C.c_int)]
+
+
 ROWLIN_MAX_ROWS = 8       # T2V_ROWLIN_MAX_ROWS
 ROWLIN_LDS_FLOATS = 16384  # t2v_rowlin_fwd: B * K of a problem (its input rows wait in LDS)
 
@@ -335,6 +345,11 @@ _SIGS = {
                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong,
                                   C.c_void_p]),
     "t2v_cd_loss_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
+    "t2v_cd_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_longlong, C.c_void_p]),
+    "t2v_ddim_reverse_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_longlong, C.c_void_p]),
+    "t2v_pack_f16_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
 }
 # Entry points of a T2V_EXPERIMENTAL=1 build only (libt2v_hip_exp.so: the measured negative results — the second t2v_gemm kernel family, the
 # one-launch feed-forward): bound when the loaded library has them.
@@ -1101,6 +1116,37 @@ class HipOps:
         assert g_loss is None or (g_loss.dtype == torch.float32 and g_loss.numel() == 1)
         self._call("t2v_cd_loss_bwd", C.byref(sched), _p(u), _p(g_loss), _p(g_model_pred), _p(d_noise_pred),
                    _DT.get(d_noise_pred.dtype, -1), B, per_clip, keep=sched)
+
+    # ---- the producer of the v2 latent records (csrc/train.hip: t2v_cd_add_noise, t2v_ddim_reverse_step, t2v_pack_f16_multi) -------------
+    def cd_add_noise(self, sched, x, noise, z, z_lp=None):
+        """z (fp32) = sqrt(acp[t_s]) x + sqrt(1 - acp[t_s]) noise per clip, t_s from ``sched``; ``z_lp``: an optional bf16 / fp16 copy
+        of z (round to nearest even) — t2v_cd_add_noise, one launch.  ``x`` / ``noise``: fp32, bf16 or fp16, a dtype each."""
+        B, per_clip = self._cd_geometry(x, noise, z, z_lp)
+        assert z.dtype == torch.float32
+        self._call("t2v_cd_add_noise", C.byref(sched), _p(x), _DT.get(x.dtype, -1), _p(noise), _DT.get(noise.dtype, -1), _p(z), _p(z_lp),
+                   -1 if z_lp is None else _DT.get(z_lp.dtype, -1), B, per_clip, keep=sched)
+
+    def ddim_reverse_step(self, sched, i, step_ratio, x, eps, prev=None, x_lp=None):
+        """Inversion step ``i`` of every clip on the fp32 state ``x``, in place (t2v_ddim_reverse_step, one launch): a clip with
+        ``index < i`` keeps its state, a clip with ``index == i`` leaves its old state in ``prev`` (fp32, optional) first; ``x_lp``:
+        an optional bf16 / fp16 copy of the state after the step.  ``eps``: fp32 or bf16."""
+        B, per_clip = self._cd_geometry(x, eps, prev, x_lp)
+        assert x.dtype == torch.float32 and (prev is None or prev.dtype == torch.float32)
+        self._call("t2v_ddim_reverse_step", C.byref(sched), int(i), int(step_ratio), _p(x), _p(eps), _DT.get(eps.dtype, -1), _p(prev),
+                   _p(x_lp), -1 if x_lp is None else _DT.get(x_lp.dtype, -1), B, per_clip, keep=sched)
+
+    def pack_f16_multi(self, entries, dst):
+        """``entries``: [(src, dst_off) or (src, dst_off, rows, dst_stride)], at most 16 contiguous fp32 / bf16 / fp16 tensors;
+        ``dst`` (fp16, contiguous) [dst_off, dst_off + src.numel()) = src.to(float16) for a flat entry; with ``rows``, row r of
+        ``src`` viewed as [rows, numel / rows] goes to dst_off + r * dst_stride — t2v_pack_f16_multi, one launch."""
+        assert dst.dtype == torch.float16 and dst.is_contiguous() and all(e[0].is_contiguous() for e in entries)
+        arr = (PackEntry * max(len(entries), 1))()
+        for d, e in zip(arr, entries):
+            src, off, rows, stride = e if len(e) == 4 else (e[0], e[1], 1, 0)
+            assert rows > 0 and src.numel() % rows == 0
+            d.src, d.n, d.rows, d.dst_off, d.dst_stride, d.dt = _p(src), src.numel() // rows, int(rows), int(off), int(stride), \
+                _DT.get(src.dtype, -1)
+        self._call("t2v_pack_f16_multi", C.cast(arr, C.c_void_p), len(entries), _p(dst), dst.numel(), keep=arr)
 
     # ---- the B-row conditioning branch (csrc/full_grad.hip: t2v_rowlin_*) ----------------------------------------------------------
     # A problem is a dict of tensors and flags, the same for the three entries (see ``t2v_rowlin_problem``): x, w, bias, res, y (fwd: the
