@@ -386,6 +386,19 @@ int t2v_lincomb3(const float* x, const float* y, const float* z, const float* ca
 int t2v_lcm_step(const float* x, const void* eps, int eps_dt, const float* noise, float sa_t,
                  float sb_t, float c_skip, float c_out, float sa_p, float sb_p, long long n,
                  float* prev, float* denoised, void* stream);
+/* Decoded video -> frames: x (B,3,T,H,W) contiguous, fp32 / bf16 / fp16 (what decode_first_stage_2DAE returns) -> out (B,T,H,W,3)
+ * uint8, one launch: the tail every entry point of the reference runs as clamp / +1 / /2 / *255 / to(uint8) / permute
+ * (predict.py:129-137, app.py, motion_prior_sample.py:299-301).  Per element: the stored value converted to fp32, NaN -> 0, otherwise
+ * y = clamp(v, -1, 1); ((y + 1) * 0.5) * 255 with every operation rounded to fp32 on its own (explicit round-to-nearest adds and
+ * multiplies, nothing contracted), truncated toward zero.  That is ((v.float().clamp(-1, 1) + 1.0) / 2.0 * 255).to(torch.uint8) bit for
+ * bit, so equality is the bound.  The reference script does the same arithmetic in the tensor's own half precision; in fp32 on the same
+ * stored values every intermediate is rounded no more coarsely, so the result is never further from the exact value.
+ * A lane takes four consecutive pixels of one frame from the three channel planes and writes their twelve contiguous bytes;
+ * neighbouring lanes write neighbouring bytes.  Lanes whose addresses are off their 4-pixel boundaries (an unaligned base, H * W
+ * not a multiple of 4) and the last pixels of such a frame move element by element.
+ * Refused before any launch: null pointers, non-positive sizes: T2V_EINVAL; a dtype code outside the above, x off its element
+ * boundary, more than 2^31 workgroups: T2V_ESHAPE. */
+int t2v_video_to_u8(const void* x, int dt, int B, int T, int H, int W, void* out, void* stream);
 
 /* ---------------------------------------------------------------- diagnostics (tools/ only)
  * Ablation bits for tools/gemm_one.py and tools/attn_one.py.  They only act in libraries built with
@@ -865,6 +878,30 @@ int t2v_cd_add_noise(const t2v_cd_sched* s, const void* x, int dt_x, const void*
 int t2v_ddim_reverse_step(const t2v_cd_sched* s, int i, int step_ratio, float* x, const void* eps, int dt_eps, float* prev, void* x_lp,
                           int dt_lp, int B, long long per_clip, void* stream);
 int t2v_pack_f16_multi(const t2v_pack_entry* table /* host */, int n_entries, void* dst, long long dst_numel, void* stream);
+
+/* ---------------------------------------------------------------- head of one step of the motion-prior guided sampler (csrc/train.hip)
+ * What motion_prior_sample.py:180-196, 283-292 computes BETWEEN the forwards of sampling step i: one launch for the whole batch.  All
+ * clips share step i, passed by value: t2v_cd_sched::index is not read and may be NULL (topk and timestep_scaling are not read
+ * either).  The latent x stays fp32, in place, between the steps, as t2v_ddim_reverse_step keeps the inverted latent.  With
+ *   t = ddim_timesteps[i], a = sqrt(alphas_cumprod[t]), sg = sqrt(1 - alphas_cumprod[t]), ap = ddim_alpha_cumprods_prev[i], w = guidance_scale:
+ *   x0c = (x - sg cond) / a, x0u = (x - sg uncond) / a       (x0_cond and x0_uncond both NULL), or
+ *   x0c = x0_cond, x0u = x0_uncond                          (both given: a cached motion_intermediate entry, used as is)
+ *   x0  = x0c + w (x0c - x0u)
+ *   eps = cond + w (cond - uncond) - sqrt(1 - a) score      (score NULL: no motion term; note a, not alphas_cumprod: the script writes
+ *                                                            (1 - alphas) ** 0.5 with alphas = sqrt(alphas_cumprod[t]); no motion_gs factor)
+ *   x  <- sqrt(ap) x0 + sqrt(1 - ap) eps
+ * cond / uncond share dt_eps, x0_cond / x0_uncond share dt_x0, score has dt_score: fp32, bf16 or fp16 each.  Optional outputs: x_lp,
+ * the new x rounded to nearest even into bf16 / fp16 (the UNet's next input); pred_x0, the CFG x0 in dt_p (fp32 / bf16 / fp16); rec,
+ * fp16 [B][5][per_clip]: the step's motion_intermediate entry in the order cond_pred_x_0 | uncond_pred_x_0 | cond_pred_noise |
+ * uncond_pred_noise | score (zeros when score is NULL), converted with the semantics documented for t2v_pack_f16_multi.
+ * Coefficients are formed in double and rounded to fp32 once (1 / a, sg / a, sqrt(ap), sqrt(1 - ap), sqrt(1 - a)); x0c and x0u are
+ * each rounded to fp32 once (they are outputs), then one fused multiply-add per line above.  Table reads are clamped; 16-byte accesses
+ * when every pointer is 16-byte aligned (rec: and per_clip a multiple of 8), scalar accesses otherwise.
+ * Refused before any launch: null x / cond / uncond / schedule tables, non-positive sizes, exactly one of x0_cond / x0_uncond given,
+ * i outside [0, n_ddim): T2V_EINVAL; a dtype code outside the above, B > T2V_CD_MAX_CLIPS: T2V_ESHAPE. */
+int t2v_mp_guided_step(const t2v_cd_sched* s, int i, float guidance_scale, float* x, const void* cond, const void* uncond, int dt_eps,
+                       const void* x0_cond, const void* x0_uncond, int dt_x0, const void* score, int dt_score, void* x_lp, int dt_lp,
+                       void* pred_x0, int dt_p, void* rec, int B, long long per_clip, void* stream);
 
 /* ---------------------------------------------------------------- recorded launch lists
  * The reference has no counterpart: its hot path is issued op by op from Python (and that is what bounds a small-batch step on

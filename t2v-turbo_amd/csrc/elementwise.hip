@@ -877,6 +877,85 @@ extern "C" int t2v_scale_multi(const t2v_adamw_tensor* table, int n_tensors, lon
     return T2V_OK;
 }
 
+// ---- decoded video -> uint8 frames (include/t2v_hip.h: t2v_video_to_u8) ------------------------------------------------------------
+// (B,3,T,H,W) -> (B,T,H,W,3): a lane takes four consecutive pixels of one frame from the three channel planes (a 16- or 8-byte load
+// each) and writes their twelve bytes as three words, so a wave writes 768 contiguous bytes.  A lane whose four addresses are not on
+// their boundaries (an unaligned base, H * W not a multiple of 4) and the last lane of a frame with fewer than four pixels move
+// element by element.  The value: every operation rounded to fp32 on its own, so that the bytes are torch's, bit for bit.
+namespace {
+#ifdef T2V_HOSTSIM   // (plain C++ on the host rounds every operation on its own)
+__device__ __forceinline__ float u8_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float u8_mul(float a, float b) { return a * b; }
+#else
+__device__ __forceinline__ float u8_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float u8_mul(float a, float b) { return __fmul_rn(a, b); }
+#endif
+__device__ __forceinline__ uint32_t u8_of(float v) {
+    if (v != v) return 0u;
+    const float y = fminf(fmaxf(v, -1.0f), 1.0f);
+    return (uint32_t)(int)u8_mul(u8_mul(u8_add(y, 1.0f), 0.5f), 255.0f);   // (in [0, 255]: truncation toward zero)
+}
+__device__ __forceinline__ float u8_h2f(uint32_t bits, int dt) {
+    if (dt == T2V_BF16) return __uint_as_float(bits << 16);
+    const uint16_t b = (uint16_t)bits;
+    _Float16 h;
+    memcpy(&h, &b, 2);
+    return (float)h;
+}
+__global__ __launch_bounds__(256) void video_to_u8_kernel(const void* __restrict__ x, int dt, int T, long long HW, long long nq, long long total,
+                                                          unsigned char* __restrict__ out) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long long bt = gid / nq, p0 = (gid - bt * nq) * 4;
+    const long long b = bt / T, t = bt - b * T;
+    const int es = dt == T2V_F32 ? 4 : 2;
+    const int n = HW - p0 < 4 ? (int)(HW - p0) : 4;
+    long long src[3];
+    uintptr_t bits = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        src[c] = ((b * 3 + c) * T + t) * HW + p0;
+        bits |= (uintptr_t)x + (uintptr_t)(src[c] * es);
+    }
+    unsigned char* o = out + (bt * HW + p0) * 3;
+    if (n == 4 && (bits & (uintptr_t)(4 * es - 1)) == 0 && ((uintptr_t)o & 3) == 0) {
+        uint32_t v[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (dt == T2V_F32) {
+                const uint4 u = *(const uint4*)((const float*)x + src[c]);
+                v[c][0] = u8_of(__uint_as_float(u.x)); v[c][1] = u8_of(__uint_as_float(u.y));
+                v[c][2] = u8_of(__uint_as_float(u.z)); v[c][3] = u8_of(__uint_as_float(u.w));
+            } else {
+                const uint2 u = *(const uint2*)((const uint16_t*)x + src[c]);
+                v[c][0] = u8_of(u8_h2f(u.x & 0xffffu, dt)); v[c][1] = u8_of(u8_h2f(u.x >> 16, dt));
+                v[c][2] = u8_of(u8_h2f(u.y & 0xffffu, dt)); v[c][3] = u8_of(u8_h2f(u.y >> 16, dt));
+            }
+        }
+        uint32_t* ow = (uint32_t*)o;   // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        ow[0] = v[0][0] | (v[1][0] << 8) | (v[2][0] << 16) | (v[0][1] << 24);
+        ow[1] = v[1][1] | (v[2][1] << 8) | (v[0][2] << 16) | (v[1][2] << 24);
+        ow[2] = v[2][2] | (v[0][3] << 8) | (v[1][3] << 16) | (v[2][3] << 24);
+        return;
+    }
+    for (int p = 0; p < n; ++p)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[3 * p + c] = (unsigned char)u8_of(load_as_f32(x, dt, src[c] + p));
+}
+}  // namespace
+
+extern "C" int t2v_video_to_u8(const void* x, int dt, int B, int T, int H, int W, void* out, void* stream) {
+    T2V_REQUIRE(x && out && B > 0 && T > 0 && H > 0 && W > 0, T2V_EINVAL, "t2v_video_to_u8: null pointer / non-positive size");
+    T2V_REQUIRE(dt == T2V_F32 || dt == T2V_BF16 || dt == T2V_F16, T2V_ESHAPE, "t2v_video_to_u8: the video is fp32, bf16 or fp16");
+    T2V_REQUIRE((uintptr_t)x % (dt == T2V_F32 ? 4 : 2) == 0, T2V_ESHAPE, "t2v_video_to_u8: the video is off its element boundary");
+    const long long HW = (long long)H * W, nq = (HW + 3) / 4, total = (long long)B * T * nq;
+    T2V_REQUIRE((total + 255) / 256 < (1ll << 31), T2V_ESHAPE, "t2v_video_to_u8: too many pixels for one launch");
+    hipLaunchKernelGGL(video_to_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dt, T, HW, nq, total,
+                       (unsigned char*)out);
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
 // ---- library state ---------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
 void t2v_set_error(const char* msg) {

@@ -350,6 +350,10 @@ _SIGS = {
     "t2v_ddim_reverse_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_longlong, C.c_void_p]),
     "t2v_pack_f16_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "t2v_mp_guided_step": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_longlong, C.c_void_p]),
+    "t2v_video_to_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 # Entry points of a T2V_EXPERIMENTAL=1 build only (libt2v_hip_exp.so: the measured negative results — the second t2v_gemm kernel family, the
 # one-launch feed-forward): bound when the loaded library has them.
@@ -1067,8 +1071,8 @@ class HipOps:
         ``ddim_timesteps`` [n_ddim] and ``index`` [B].  The struct holds raw pointers: the caller keeps the tensors alive."""
         for t in (alphas_cumprod, ddim_alpha_cumprods_prev):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
-        for t in (ddim_timesteps, index):
-            assert t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1
+        for t in (ddim_timesteps, index):          # (``index`` None: for the entry points that take their step by value)
+            assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1)
         assert ddim_timesteps.numel() == ddim_alpha_cumprods_prev.numel()
         return CdSched(_p(alphas_cumprod), _p(ddim_timesteps), _p(ddim_alpha_cumprods_prev), _p(index), alphas_cumprod.numel(),
                        ddim_timesteps.numel(), int(topk), float(timestep_scaling))
@@ -1147,6 +1151,30 @@ class HipOps:
             d.src, d.n, d.rows, d.dst_off, d.dst_stride, d.dt = _p(src), src.numel() // rows, int(rows), int(off), int(stride), \
                 _DT.get(src.dtype, -1)
         self._call("t2v_pack_f16_multi", C.cast(arr, C.c_void_p), len(entries), _p(dst), dst.numel(), keep=arr)
+
+    # ---- the motion-prior guided sampler (csrc/train.hip: t2v_mp_guided_step; csrc/elementwise.hip: t2v_video_to_u8) -----------------------
+    def mp_guided_step(self, sched, i, guidance_scale, x, cond, uncond, x0_cond=None, x0_uncond=None, score=None, x_lp=None, pred_x0=None,
+                       rec=None):
+        """The head of sampling step ``i`` on the fp32 state ``x``, in place (t2v_mp_guided_step, one launch for the whole batch):
+        CFG x0 and noise estimate from ``cond`` / ``uncond`` (one dtype), minus ``sqrt(1 - a) score`` when ``score`` is given, then
+        the DDIM step.  ``x0_cond`` / ``x0_uncond``: both None (formed from ``x``) or both given (a cached entry).  Optional outputs:
+        ``x_lp`` (bf16 / fp16 copy of the new state), ``pred_x0`` (the CFG x0), ``rec`` (fp16 [B, 5, ...]: the step's
+        motion_intermediate entry).  ``sched``: ``cd_sched`` (its index may be None)."""
+        B, per_clip = self._cd_geometry(x, cond, uncond, x0_cond, x0_uncond, score, x_lp, pred_x0)
+        assert x.dtype == torch.float32 and cond.dtype == uncond.dtype
+        assert x0_cond is None or x0_uncond is None or x0_cond.dtype == x0_uncond.dtype
+        assert rec is None or (rec.dtype == torch.float16 and rec.is_contiguous() and rec.numel() == 5 * x.numel())
+        dt = lambda t: -1 if t is None else _DT.get(t.dtype, -1)   # noqa: E731
+        self._call("t2v_mp_guided_step", C.byref(sched), int(i), float(guidance_scale), _p(x), _p(cond), _p(uncond), dt(cond), _p(x0_cond),
+                   _p(x0_uncond), dt(x0_cond if x0_cond is not None else x0_uncond), _p(score), dt(score), _p(x_lp), dt(x_lp), _p(pred_x0),
+                   dt(pred_x0), _p(rec), B, per_clip, keep=sched)
+
+    def video_to_u8(self, video, out):
+        """``video`` (B,3,T,H,W) contiguous fp32 / bf16 / fp16 -> ``out`` (B,T,H,W,3) uint8 =
+        ``((video.float().clamp(-1, 1) + 1.0) / 2.0 * 255).to(torch.uint8)`` permuted, NaN -> 0 — t2v_video_to_u8, one launch."""
+        B, ch, T, H, W = video.shape
+        assert ch == 3 and video.is_contiguous() and out.is_contiguous() and out.dtype == torch.uint8 and tuple(out.shape) == (B, T, H, W, 3)
+        self._call("t2v_video_to_u8", _p(video), _DT.get(video.dtype, -1), B, T, H, W, _p(out))
 
     # ---- the B-row conditioning branch (csrc/full_grad.hip: t2v_rowlin_*) ----------------------------------------------------------
     # A problem is a dict of tensors and flags, the same for the three entries (see ``t2v_rowlin_problem``): x, w, bias, res, y (fwd: the

@@ -98,7 +98,11 @@ class T2VTurboVC2Pipeline:
             latents, denoised = self.scheduler.step(model_pred, i, t, latents, generator=generator, return_dict=False)
         if output_type == "latent":
             return denoised
-        return self.pretrained_t2v.decode_first_stage_2DAE(denoised)
+        videos = self.pretrained_t2v.decode_first_stage_2DAE(denoised)
+        if output_type == "uint8":          # (B,T,H,W,3) frames: the clamp / scale / cast / permute tail of predict.py:129-137 in one launch
+            from .motion_prior import video_to_uint8
+            return video_to_uint8(videos)
+        return videos
 
 
 def make_synthetic_t2v(unet, device, dtype, ddconfig=None):
