@@ -352,6 +352,15 @@ int t2v_attn_spatial(const void* q, int ldq, const void* k, int ldk, const void*
                      long long vt_img_stride, void* out, int ldo, int n_img, int seq_q, int seq_kv,
                      int heads, int kv_div, float scale, void* stream);
 
+/* The same kernel for spatial SELF-attention (seq_q == seq_kv == seq, kv_div == 1) with V in its token rows: q, k and v are bf16 rows
+ * (img*seq + i), head h at columns [h*64, h*64+64) — typically three column ranges of one q|k|v Linear's output.  The V tile goes
+ * to LDS row-major and is consumed through the transposing LDS read of gfx950; rows past seq of the last key tile come from the
+ * library's zero page for K and V alike, so no operand is padded or zero-filled and nothing outside the n_img*seq rows and the
+ * heads*64 columns of each operand is read.  The products are summed in the order of t2v_attn_spatial: for equal operands the two
+ * entry points give bit-identical outputs.  ldq, ldk, ldv % 8 == 0, ldo % 4 == 0, all >= heads*64. */
+int t2v_attn_spatial_rm(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                        int n_img, int seq, int heads, float scale, void* stream);
+
 /* Temporal self-attention, head dim 64, sequence = frames: for every (clip b, pixel p, head h)
  * softmax(Q K^T * scale) V over the F frames, reading rows ((b*F+f)*HW + p) directly from the
  * token-major q/k/v (no '(b h w) t c' rearrange copies, attention.py:475-511,102-164).

@@ -9,6 +9,8 @@
 //   enumerated in the order the score registers come out, and V^T is read from LDS in that order,
 //   so P never goes through LDS or cross-lane shuffles (K rows sit in LDS with bits 2/3 of the key index
 //   swapped, which makes each lane's 8 contraction keys one contiguous 16-byte chunk of V^T).
+//   VROW form (t2v_attn_spatial_rm, self-attention): V stays in its token rows — q | k | v are three column ranges of ONE Linear's
+//   output — and the tile [64 keys][64 d] is read back with ds_read_b64_tr_b16 (two per fragment), same contraction enumeration.
 // attn_temporal_kernel: the sequence is the F (=16) frames of one pixel; one wave per
 //   (clip, pixel, head), rows fetched with the frame stride straight from the token-major
 //   buffers (no rearrange copies); tiny FLOPs, bandwidth bound.
@@ -49,6 +51,60 @@ constexpr int K_TILE_BYTES = KT * 128;
 constexpr int VT_TILE_BYTES = 64 * 128;
 constexpr int AT_STAGE = K_TILE_BYTES + VT_TILE_BYTES;
 
+// ds_read_b64_tr_b16 (gfx950): every lane supplies the LDS address of FOUR contiguous 16-bit elements (8-byte aligned); within each
+// group of 16 lanes, lane l receives element (l & 3) of the values read by lanes (l >> 2), 4 + (l >> 2), 8 + (l >> 2), 12 + (l >> 2)
+// (csrc/wgrad_tn.hip's helper with its host-simulator branch; measured lane mapping: tools/probes/tr_b16_probe.cpp).  EXEC must be
+// all ones.  Here the read is inline assembly (address p + OFF, OFF in the instruction's offset field), not the builtin: the
+// compiler puts an s_waitcnt vmcnt(0) in front of the builtin while an LDS-DMA fill is in flight (it cannot tell that the fill goes
+// to the OTHER stage), which would serialise the prefetch of tile t + 1 with the products of tile t.  The compiler does not count
+// these reads: their results may be used only behind the s_waitcnt of vrow_join().
+template <int OFF>
+__device__ __forceinline__ uint64_t lds_read_tr16(const char* p, int lane) {
+#ifdef T2V_HOSTSIM
+    uint64_t mine;
+    memcpy(&mine, p + OFF, 8);
+    uint64_t out = 0;
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t v = __shfl(mine, (lane & ~15) + 4 * j + ((lane & 15) >> 2), 64);
+        out |= ((v >> (16 * (lane & 3))) & 0xffffull) << (16 * j);
+    }
+    return out;
+#else
+    (void)lane;
+    uint64_t v;
+    const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(OFF) : "memory");
+    return v;
+#endif
+}
+// the raw reads of K-step KS (keys KS * 16 + 8 hi + 0..3 / 4..7 of d = db * 32 + l31) from the V tile: see vtr[] in the kernel
+template <int KS>
+__device__ __forceinline__ void vrow_reads(const char* sv, const int (&vtr)[2], int lane, uint64_t (&raw)[4][2][2]) {
+#pragma unroll
+    for (int db = 0; db < 2; ++db) {
+        raw[KS][db][0] = lds_read_tr16<KS * 2048>(sv + vtr[db], lane);
+        raw[KS][db][1] = lds_read_tr16<KS * 2048 + 1024>(sv + vtr[db], lane);
+    }
+}
+// every LDS read issued so far has landed.  The 16 raw halves are tied to the wait — no use, and no copy into a fragment's register
+// tuple, can be scheduled in front of it — and only then joined into the eight MFMA operands.
+__device__ __forceinline__ void vrow_join(uint64_t (&raw)[4][2][2], bf16x8_t (&f)[4][2]) {
+#ifndef T2V_HOSTSIM
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(raw[0][0][0]), "+v"(raw[0][0][1]), "+v"(raw[0][1][0]), "+v"(raw[0][1][1]), "+v"(raw[1][0][0]), "+v"(raw[1][0][1]),
+                   "+v"(raw[1][1][0]), "+v"(raw[1][1][1]), "+v"(raw[2][0][0]), "+v"(raw[2][0][1]), "+v"(raw[2][1][0]), "+v"(raw[2][1][1]),
+                   "+v"(raw[3][0][0]), "+v"(raw[3][0][1]), "+v"(raw[3][1][0]), "+v"(raw[3][1][1]));
+#endif
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            const uint64_t lo = raw[ks][db][0], hi = raw[ks][db][1];
+            const uint4 u = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+            f[ks][db] = *(const bf16x8_t*)&u;
+        }
+}
+
 __device__ __forceinline__ void dma16(const void* gsrc, char* lds_dst_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst_wave_base, 16, 0, 0);
@@ -58,6 +114,12 @@ __device__ __forceinline__ void dma16(const void* gsrc, char* lds_dst_wave_base)
 // XOR-swizzled by (row>>1)&7, are filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, no
 // ds_write): 16 wave-instructions per tile pair, 4 per wave.  Keys past seq_kv: K rows come from a zero
 // page; the V^T buffer's padding columns must be finite (the engine zero-fills them) since their P is 0.
+// VROW: the second tile is V itself, [64 keys][64 d] with the K tile's row order (row r = key perm(r)) and zero-page rows past
+// seq_kv, so nothing has to be padded or zero-filled.  Its 16-byte chunk index is XORed with 4 * ((row >> 1) & 1): a transposing read
+// of a 32-lane half takes 4 rows (one aligned group of 4) x 64 bytes, rows r and r + 2 start on the same bank (128-byte rows, 64
+// banks) and the XOR sends their 64 bytes to opposite halves of the row — bank = 32 (q & 1) + 16 (db ^ (q >> 1)) + 8 g16 + 2 p
+// (+ 0, 1) over the half's lanes (row q, column group g16, 8-byte piece p): every bank once.  The DMA fill is lane-linear in LDS
+// whatever the XOR (it only picks which global chunk a lane fetches, within one 128-byte row segment).
 #ifndef T2V_ATTN_WPE
 #define T2V_ATTN_WPE 3  // waves per SIMD the register budget is sized for (tools: -DT2V_ATTN_WPE=2 / 4 variants for A/B runs)
 #endif
@@ -67,7 +129,7 @@ __device__ __forceinline__ void dma16(const void* gsrc, char* lds_dst_wave_base)
 // stream changes nothing (224-228 vs 224 us at four waves per SIMD; 240-244 vs 211-220 us at three, where only one eight-wave workgroup
 // fits a CU) — the launch is not fill-bound; with r05_attn_pmc.csv (VALU active 45 %, matrix pipe 26 %, 11.7 VALU per MFMA) it runs at
 // the sum of the softmax's VALU work and the MFMA work of the same wave.  The library launches NW = 4.
-template <int NW>
+template <int NW, bool VROW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATTN_WPE, T2V_ATTN_WPE))) void attn_spatial_kernel(const bf16_t* __restrict__ q, int ldq,
                                                            const bf16_t* __restrict__ k, int ldk,
                                                            const bf16_t* __restrict__ vt, int ld_vt, long long vt_img_stride,
@@ -93,16 +155,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
         }
     }
     const bf16_t* kbase = k + (long long)img_kv * seq_kv * ldk + head * 64;
-    const bf16_t* vbase = vt + (long long)img_kv * vt_img_stride + (long long)head * 64 * ld_vt;
+    // VROW: `vt` is V in token rows (row stride ld_vt), indexed like K
+    const bf16_t* vbase = VROW ? vt + (long long)img_kv * seq_kv * ld_vt + head * 64
+                               : vt + (long long)img_kv * vt_img_stride + (long long)head * 64 * ld_vt;
     const int ntile = (seq_kv + KT - 1) / KT;
 
     // DMA lane roles: wave-instruction i (= wave + NW*j, j < 8 / NW) covers tile rows [8i, 8i+8)
     constexpr int DJ = 8 / NW;
-    int drow[DJ], dchunk[DJ];
+    int drow[DJ], dchunk[DJ], vchunk[DJ];
 #pragma unroll
     for (int j = 0; j < DJ; ++j) {
         drow[j] = (wave + NW * j) * 8 + (lane >> 3);
         dchunk[j] = ((lane & 7) ^ ((drow[j] >> 1) & 7)) * 8;
+        vchunk[j] = ((lane & 7) ^ (((drow[j] >> 1) & 1) << 2)) * 8;
     }
     auto stage = [&](int t, int buf) {
         char* sk = smem + buf * AT_STAGE;
@@ -116,7 +181,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
             const int key = key0 + ((drow[j] & ~12) | ((drow[j] & 4) << 1) | ((drow[j] & 8) >> 1));
             const bf16_t* ksrc = key < seq_kv ? kbase + (long long)key * ldk + dchunk[j] : zero;
             dma16(ksrc, sk + (wave + NW * j) * 1024);
-            dma16(vbase + (long long)drow[j] * ld_vt + key0 + dchunk[j], sv + (wave + NW * j) * 1024);
+            if constexpr (VROW) {
+                const bf16_t* vsrc = key < seq_kv ? vbase + (long long)key * ld_vt + vchunk[j] : zero;
+                dma16(vsrc, sv + (wave + NW * j) * 1024);
+            } else {
+                dma16(vbase + (long long)drow[j] * ld_vt + key0 + dchunk[j], sv + (wave + NW * j) * 1024);
+            }
         }
     };
 
@@ -126,6 +196,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
     float m_run = -INFINITY, l_run = 0.f;
     const int swz = (lane >> 1) & 7;
     const float c2 = scale * 1.4426950408889634f;  // softmax in base 2
+    // VROW: this lane's transposing-read address inside the V tile, per d-block db.  Lane 4 vq + vp of a 16-lane group points at
+    // [key t0 + vq][d = db * 32 + 16 g16 + 4 vp] and receives keys t0 .. t0 + 3 of d = db * 32 + l31; K-step ks takes t0 = ks * 16 +
+    // 8 hi (+ 4 for the second read), which the row order of the tile puts at row ks * 16 + 4 hi + vq (+ 8): + ks * 2048 (+ 1024).
+    int vtr[2];
+    {
+        const int vq = (lane >> 2) & 3, vp = lane & 3, g16 = (lane >> 4) & 1;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+            vtr[db] = (4 * hi + vq) * 128 + (((4 * db + 2 * g16 + (vp >> 1)) ^ ((vq >> 1) << 2)) << 4) + 8 * (vp & 1);
+    }
 
     stage(0, 0);
     for (int t = 0; t < ntile; ++t) {
@@ -181,11 +261,21 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
 #else
         constexpr int VF_EARLY = 4;
 #endif
+        uint64_t vraw[4][2][2];   // VROW: the two transposing reads of each fragment (4 keys each), joined behind the softmax
+        if constexpr (VROW) {
+            vrow_reads<0>(sv, vtr, lane, vraw);
+            vrow_reads<1>(sv, vtr, lane, vraw);
+            if constexpr (VF_EARLY == 4) {
+                vrow_reads<2>(sv, vtr, lane, vraw);
+                vrow_reads<3>(sv, vtr, lane, vraw);
+            }
+        } else {
 #pragma unroll
-        for (int ks = 0; ks < VF_EARLY; ++ks)
+            for (int ks = 0; ks < VF_EARLY; ++ks)
 #pragma unroll
-            for (int db = 0; db < 2; ++db)
-                vfr[ks][db] = *(const bf16x8_t*)(sv + (db * 32 + l31) * 128 + (((ks * 2 + hi) ^ swz) << 4));
+                for (int db = 0; db < 2; ++db)
+                    vfr[ks][db] = *(const bf16x8_t*)(sv + (db * 32 + l31) * 128 + (((ks * 2 + hi) ^ swz) << 4));
+        }
         T2V_ATTN_FENCE();
         // ---- online softmax (this lane: one query, 32 of the 64 keys; partner lane^32 the rest) ---
         // scores stay raw; max is taken on them and exp2(fma(s, c, -c*max)) folds scale*log2(e): 3 VALU
@@ -232,11 +322,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(T2V_ATT
             l_run += lsum;
         }
         // ---- O^T += V^T P^T: the score registers already come out in contraction order ----------------------
+        if constexpr (VROW) {
+            if constexpr (VF_EARLY < 4) {
+                vrow_reads<2>(sv, vtr, lane, vraw);
+                vrow_reads<3>(sv, vtr, lane, vraw);
+            }
+            vrow_join(vraw, vfr);
+        } else {
 #pragma unroll
-        for (int ks = VF_EARLY; ks < 4; ++ks)
+            for (int ks = VF_EARLY; ks < 4; ++ks)
 #pragma unroll
-            for (int db = 0; db < 2; ++db)
-                vfr[ks][db] = *(const bf16x8_t*)(sv + (db * 32 + l31) * 128 + (((ks * 2 + hi) ^ swz) << 4));
+                for (int db = 0; db < 2; ++db)
+                    vfr[ks][db] = *(const bf16x8_t*)(sv + (db * 32 + l31) * 128 + (((ks * 2 + hi) ^ swz) << 4));
+        }
         T2V_ATTN_PRIO(1);
         if (!ATT_ABL(2))
 #pragma unroll
@@ -435,9 +533,27 @@ extern "C" int t2v_attn_spatial(const void* q, int ldq, const void* k, int ldk, 
     T2V_REQUIRE(vt_img_stride % 8 == 0, T2V_ESHAPE, "t2v_attn_spatial: vt_img_stride");
     {
         dim3 grid((seq_q + 127) / 128, heads, n_img);
-        hipLaunchKernelGGL(attn_spatial_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, ldq,
+        hipLaunchKernelGGL((attn_spatial_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, ldq,
                            (const bf16_t*)k, ldk, (const bf16_t*)vt, ld_vt, vt_img_stride, (bf16_t*)out, ldo, seq_q, seq_kv, heads,
                            kv_div, scale, (const bf16_t*)t2v_zero_page(), g_attn_debug);
+    }
+    T2V_CHECK_LAUNCH();
+    return T2V_OK;
+}
+
+extern "C" int t2v_attn_spatial_rm(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                   int n_img, int seq, int heads, float scale, void* stream) {
+    T2V_REQUIRE(q && k && v && out, T2V_EINVAL, "t2v_attn_spatial_rm: null pointer");
+    T2V_REQUIRE(n_img > 0 && seq > 0 && heads > 0, T2V_EINVAL, "t2v_attn_spatial_rm: bad size");
+    T2V_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, T2V_ESHAPE, "t2v_attn_spatial_rm: strides");
+    T2V_REQUIRE(ldq >= heads * 64 && ldk >= heads * 64 && ldv >= heads * 64 && ldo >= heads * 64, T2V_ESHAPE,
+                "t2v_attn_spatial_rm: row stride smaller than heads * 64");
+    T2V_REQUIRE(heads <= 65535 && n_img <= 65535, T2V_ESHAPE, "t2v_attn_spatial_rm: grid");
+    {
+        dim3 grid((seq + 127) / 128, heads, n_img);
+        hipLaunchKernelGGL((attn_spatial_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, ldq,
+                           (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0ll, (bf16_t*)out, ldo, seq, seq, heads, 1, scale,
+                           (const bf16_t*)t2v_zero_page(), g_attn_debug);
     }
     T2V_CHECK_LAUNCH();
     return T2V_OK;

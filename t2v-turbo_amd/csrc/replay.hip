@@ -71,7 +71,7 @@ const Entry kTable[] = {
     T2V_ENTRY(t2v_sumsq), T2V_ENTRY(t2v_gather_f32), T2V_ENTRY(t2v_attn_spatial_bwd), T2V_ENTRY(t2v_wgrad_tn), T2V_ENTRY(t2v_wgrad_tn_group),
     T2V_ENTRY(t2v_transpose_pad_bf16), T2V_ENTRY(t2v_dropout_bf16), T2V_ENTRY(t2v_im2col_bf16), T2V_ENTRY(t2v_gn_coef_cs), T2V_ENTRY(t2v_norm_affine_grad),
     T2V_ENTRY(t2v_rowlin_fwd), T2V_ENTRY(t2v_rowlin_bwd_data), T2V_ENTRY(t2v_rowlin_wgrad), T2V_ENTRY(t2v_timestep_embedding_f32), T2V_ENTRY(t2v_dropout_f32),
-    T2V_ENTRY(t2v_rank_loss), T2V_ENTRY(t2v_ema_multi),
+    T2V_ENTRY(t2v_rank_loss), T2V_ENTRY(t2v_ema_multi), T2V_ENTRY(t2v_attn_spatial_rm),
 };
 constexpr int kEntries = (int)(sizeof(kTable) / sizeof(kTable[0]));
 

@@ -258,6 +258,10 @@ class _Engine:
     # norm1 / norm2 -> q | k | v and every block's norm3 -> GEGLU projection at the 320- and 640-channel levels — no t2v_layernorm launch,
     # no normalised tensor.  T2V_LN_IN=0: the separate launch.
     ln_in_fill = os.environ.get("T2V_LN_IN", "1") == "1"
+    # Spatial self-attention on ONE q | k | v Linear with V read from its token rows (t2v_attn_spatial_rm): per block no V^T GEMM, no
+    # zero-fill, and no t2v_layernorm launch where the panel fill normalises.  T2V_ATTN_VROW=0: the q|k + V^T route (A/B runs).  A
+    # backend without the op (the emulated one) keeps that route as well.
+    attn_vrow = os.environ.get("T2V_ATTN_VROW", "1") == "1"
 
     def linear_ln_in(self, a, norm, *, w, bias, act=nt.ACT_NONE):
         """Linear(LayerNorm(a)) as ONE t2v_linear_pr launch, or None where that kernel does not take the launch (the caller normalises first)."""
@@ -969,6 +973,19 @@ class UNetEngine(_Engine):
             self.pool.put(qkv)
             return o
 
+        def spatial_self_attn_rm(attn, norm, src):
+            """q | k | v of LayerNorm(src) as ONE GEMM (the temporal blocks' form) and t2v_attn_spatial_rm on its three column
+            ranges: no V^T GEMM, no V^T buffer, no zero-fill — and no LayerNorm launch where t2v_linear_pr normalises in its panel
+            fill.  ``src`` is ``box["ln"]`` when norm1 has been applied already."""
+            w = pk.cat_mats([attn.to_q, attn.to_k, attn.to_v], "qkv")
+            qkv = self.linear_ln_in(src, norm, w=w, bias=None) if src is not box["ln"] else None
+            if qkv is None:
+                qkv = self.linear(lnorm(norm, src) if src is not box["ln"] else src, None, w=w, bias=None)
+            o = self.buf(M, inner)
+            ops.attn_spatial_rm(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], o, n_img, hw, attn.heads, attn.scale)
+            self.pool.put(qkv)
+            return o
+
         def spatial_self_attn(attn, src):
             qk = self.linear(src, None, w=pk.cat_mats([attn.to_q, attn.to_k], "qk"), bias=None)
             kp = ((hw + 63) // 64) * 64
@@ -997,6 +1014,8 @@ class UNetEngine(_Engine):
         # producer overwrites the shared buffer (stream order), fused or not.
         if temporal:
             o = temporal_attn(a1, blk.norm1, ln1 if ln1 is not None else y, rs)
+        elif self.attn_vrow and hasattr(ops, "attn_spatial_rm"):
+            o = spatial_self_attn_rm(a1, blk.norm1, ln1 if ln1 is not None else y)
         else:  # two consumers (q|k and V^T, the latter with the tokens as its column operand): the LayerNorm stays a launch
             o = spatial_self_attn(a1, ln1 if ln1 is not None else lnorm(blk.norm1, y))
         # row statistics only where the next LayerNorm will be folded: the spatial block's norm2 (-> cross-attention q)

@@ -27,6 +27,8 @@ def algo_bytes(name, a):
     if name == "t2v_attn_spatial":
         n_img, sq, skv, heads, kv_div = a[9], a[10], a[11], a[12], a[13]
         return 2.0 * 64 * heads * (2 * n_img * sq + 2 * (n_img // kv_div) * skv)
+    if name == "t2v_attn_spatial_rm":   # (q, ldq, k, ldk, v, ldv, out, ldo, n_img, seq, heads, ...): q, k, v in + out
+        return 2.0 * 64 * a[10] * 4 * a[8] * a[9]
     return 0.0
 
 
