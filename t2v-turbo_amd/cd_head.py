@@ -78,8 +78,7 @@ def _ops_for(t, ops):
     if ops is not None:
         return ops
     if t.is_cuda and native_enabled():
-        from .optim import _shared_ops
-        return _shared_ops()
+        return nt.shared_ops()
     return None
 
 

@@ -10,6 +10,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .native import shared_ops
+
 
 def init_distributed(backend=None, single_process_group=False):
     """Initialise from the torchrun environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).  The rank's GPU becomes the
@@ -103,12 +105,11 @@ class FlatGradSync:
     def clip_grad_norm_(self, max_norm):
         """Global L2 clip on the (already averaged) flat buffer (accelerator.clip_grad_norm_)."""
         if self.flat.is_cuda and self.flat.dtype == torch.float32:  # deterministic two-pass sum of squares (t2v_sumsq), no ATen reduction
-            from .optim import _shared_ops
             if getattr(self, "_norm_ws", None) is None:
                 self._norm_ws = torch.empty(1025, dtype=torch.float32, device=self.flat.device)
             try:
                 with torch.cuda.device(self.flat.device):
-                    _shared_ops().sumsq(self.flat, self._norm_ws[:1024], self._norm_ws[1024:])
+                    shared_ops().sumsq(self.flat, self._norm_ws[:1024], self._norm_ws[1024:])
                 norm = self._norm_ws[1024].sqrt()
             except Exception as e:  # noqa: BLE001 - the clip is exchange plumbing, not the hot path: say so and use torch's norm
                 import warnings

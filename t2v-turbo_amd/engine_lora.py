@@ -176,7 +176,7 @@ class LoraTrainMixin:
         Contract: a write that moves no version counter (through ``p.data``, or through a flat buffer the tensors are ``.data``
         views of — a restored ``flat_param``, an EMA or a custom optimizer on the flat buffer) must call
         ``invalidate_lora_packs()``.  ``FlatAdamW.step`` and ``update_ema_flat`` do NOT call it: they write through the flat buffer and
-        then TOUCH one tensor's version counter on purpose (``add_(0.0)``), which is what this fingerprint sees — do not remove
+        then TOUCH one tensor's version counter on purpose (``optim.touch``), which is what this fingerprint sees — do not remove
         that touch on the strength of an invalidation hook that nothing registers."""
         fp = 0
         for p in self.lora_params:   # every version counter and every data pointer (re-homing of ANY tensor is seen)

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import cd_head, cd_math
+from .native import RANK_LOSS_MAX, shared_ops
 
 MOTION_INTERMEDIATE_KEYS = ("cond_pred_x_0", "uncond_pred_x_0", "cond_pred_noise", "uncond_pred_noise", "score")
 
@@ -98,9 +99,7 @@ def compute_temp_loss_fused(attention_prob, attention_prob_example, rank_k=1, sc
             loss = loss + (d * d).sum() / count
             grads[nm] = (alpha * 2.0 / count * d).to(gens[nm].dtype)
         return alpha * loss, grads
-    from .native import RANK_LOSS_MAX
-    from .optim import _shared_ops
-    ops = _shared_ops()
+    ops = shared_ops()
     dev = gens[names[0]].device
     loss_p = torch.empty(P, dtype=torch.float32, device=dev)
     by_n = {}
@@ -178,7 +177,6 @@ def video_to_uint8(videos):
     with the channels last; NaN gives 0.  CUDA: one launch (``t2v_video_to_u8``), the same bytes."""
     assert videos.dim() == 5 and videos.shape[1] == 3, "video_to_uint8: (B,3,T,H,W)"
     if videos.is_cuda:
-        from .optim import _shared_ops
         v = videos.detach()
         if v.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             v = v.float()
@@ -186,7 +184,7 @@ def video_to_uint8(videos):
         B, _, T, H, W = v.shape
         out = torch.empty((B, T, H, W, 3), dtype=torch.uint8, device=v.device)
         with torch.cuda.device(v.device):
-            _shared_ops().video_to_u8(v, out)
+            shared_ops().video_to_u8(v, out)
         return out
     v = torch.nan_to_num(videos.detach().float(), nan=-1.0)
     return ((v.clamp(-1.0, 1.0) + 1.0) / 2.0 * 255).to(torch.uint8).permute(0, 2, 3, 4, 1).contiguous()
@@ -461,9 +459,8 @@ def motion_prior_sample(unet, solver, noise_scheduler, original_latents, interme
             noise, float(guidance_scale), guided, temp_loss_scale, cached, return_sampled, reward, span)
     try:
         if native:
-            from .optim import _shared_ops
             with torch.cuda.device(original_latents.device):
-                latents, entries, sampled, forwards, copies = _sample_native(_shared_ops(), *args)
+                latents, entries, sampled, forwards, copies = _sample_native(shared_ops(), *args)
         else:
             latents, entries, sampled, forwards, copies = _sample_torch(*args)
     finally:

@@ -1248,3 +1248,14 @@ class HipOps:
     def lcm_step(self, x, eps, noise, sa_t, sb_t, c_skip, c_out, sa_p, sb_p, prev, denoised):
         self._call("t2v_lcm_step", _p(x), _p(eps), _DT[eps.dtype], _p(noise), sa_t, sb_t, c_skip, c_out, sa_p, sb_p,
                    x.numel(), _p(prev), _p(denoised))
+
+
+_OPS = None
+
+
+def shared_ops():
+    """The one ``HipOps`` of the process for launches outside an engine: optimizers, EMA, heads (its constructor parses the tune table)."""
+    global _OPS
+    if _OPS is None:
+        _OPS = HipOps()
+    return _OPS

@@ -1,20 +1,133 @@
-"""Flat-buffer AdamW / gradient clip / EMA: the LoRA tensors, their gradients
-(``dist.FlatGradSync``) and the optimizer moments each live in ONE contiguous fp32 buffer, so an optimizer
-step is one fused HIP kernel (``t2v_adamw_step``) instead of bitsandbytes' CUDA-only 8-bit AdamW
-(train_t2v_turbo_v1_lora.py:765-803) or 1150 small torch launches; the clip coefficient of
-``clip_grad_norm_`` (:1193) is folded into the same pass.  On CPU tensors the same arithmetic runs in torch.
-
-``AdamW8bit`` (below ``FlatAdamW``) is the ``torch.optim.Optimizer`` the reference's ``--use_8bit_adam`` asks for
-(``bnb.optim.AdamW8bit``): parameters and gradients stay where the trainer put them, the two moments are stored block-wise in
-8 bits (``t2v_adamw8_step``, one launch for every tensor).  ``compat.install()`` serves it as ``bitsandbytes.optim.AdamW8bit``.
-
-``AdamW`` (at the end) is its fp32 counterpart, the trainers' default without that flag: ``torch.optim.AdamW``'s constructor, state and
-checkpoints, one ``t2v_adamw_multi`` launch per step.  ``clip_grad_norm_`` / ``grad_clip_coef`` are the gradient clipping in front of it
-(``t2v_sumsq_multi``, ``t2v_scale_multi``): the norm and the coefficient stay on the device."""
+"""The optimizer side of a training step.  ``FlatAdamW`` keeps the LoRA tensors, their gradients (``dist.FlatGradSync``) and the moments
+each in ONE contiguous fp32 buffer: a step is one fused kernel (``t2v_adamw_step``) with the clip coefficient of ``clip_grad_norm_``
+(train_t2v_turbo_v1_lora.py:1193) folded in, ``update_ema_flat`` its EMA.  Everything else leaves the tensors where the trainer put them
+and walks a device table of them in one launch: ``AdamW8bit`` (``t2v_adamw8_step``: the ``bnb.optim.AdamW8bit`` of ``--use_8bit_adam``,
+moments block-wise in 8 bits, served as ``bitsandbytes.optim.AdamW8bit`` by ``compat.install()``), ``AdamW`` (``t2v_adamw_multi``:
+``torch.optim.AdamW``'s constructor, state and checkpoints), ``clip_grad_norm_`` / ``grad_clip_coef`` (``t2v_sumsq_multi``,
+``t2v_scale_multi``: norm and coefficient stay on the device) and ``update_ema`` (``t2v_ema_multi``).  These four share ONE table path,
+the section below: the record layouts are the ctypes classes of ``native.py`` (``record_dtype``), ``work_blocks`` gives every tensor its
+first work block, ``ema_table`` / ``adamw8_table`` / ``adamw_table`` fill the records, ``upload`` puts them on the device, ``_Recent`` keeps
+the plans of the last few tensor lists, ``touch`` tells the engines that a kernel wrote parameters.  CPU tensors: the same arithmetic in torch."""
+import contextlib
 import operator
 
 import numpy as np
 import torch
+
+from . import native as nt
+from .native import shared_ops, shared_ops as _shared_ops   # (``_shared_ops``: its name while it lived here)
+
+QBLOCK = nt.ADAMW8_BLOCK       # elements per quantisation block (T2V_ADAMW8_BLOCK)
+MAX_HYPER = nt.ADAMW_MAX_HYPER  # T2V_ADAMW_MAX_HYPER
+
+# ------------------------------------------------------------------------------------------------ descriptor tables
+_T = torch.Tensor
+_dtype_of, _is_cuda = operator.attrgetter("dtype"), operator.attrgetter("is_cuda")
+
+
+def record_dtype(struct):
+    """The numpy record dtype of a ctypes ``Structure`` of ``native.py``: its field names, offsets and size, pointers as ``<u8``."""
+    return np.dtype(struct)
+
+
+def work_blocks(numel, block):
+    """-> (work0 of every tensor, total): each tensor takes ceil(numel / block) work blocks of one launch, in order."""
+    blocks = (np.asarray(numel, dtype=np.int64) + (block - 1)) // block
+    return np.cumsum(blocks) - blocks, int(blocks.sum())
+
+
+def _ptrs(tensors):
+    return np.fromiter(map(_T.data_ptr, tensors), dtype=np.uint64, count=len(tensors))
+
+
+def _numels(tensors):
+    return np.fromiter(map(_T.numel, tensors), dtype=np.int64, count=len(tensors))
+
+
+def ema_table(targets, sources):
+    """The ``t2v_ema_tensor`` records of the pairs, in order -> (numpy record array, work blocks of the launch)."""
+    host = np.zeros(len(targets), dtype=record_dtype(nt.EmaTensor))
+    host["target"], host["src"], host["n"] = _ptrs(targets), _ptrs(sources), _numels(targets)
+    host["work0"], work = work_blocks(host["n"], nt.EMA_BLOCK)
+    host["src_dt"] = [nt.BF16 if s.dtype == torch.bfloat16 else nt.F32 for s in sources]
+    return host, work
+
+
+def adamw8_table(params, grads, state_blocks, f32_state, lr=0.0, weight_decay=0.0, launch_of=None):
+    """The ``t2v_adamw8_tensor`` records of the tensors, in order -> (numpy record array, launches).  ``state_blocks``: every tensor's
+    first block in its state arena; ``f32_state``: fp32 moments? (one value or one per tensor, as ``lr`` and ``weight_decay``);
+    ``launch_of``: its launch, non-decreasing (None: one).  ``launches``: ``(first record, end record, work blocks)`` each."""
+    n = len(params)
+    host = np.zeros(n, dtype=record_dtype(nt.Adamw8Tensor))
+    host["param"], host["grad"], host["state_block"], host["n"] = _ptrs(params), _ptrs(grads), state_blocks, _numels(params)
+    host["lr"], host["weight_decay"] = lr, weight_decay
+    host["flags"] = np.where(f32_state, nt.ADAMW8_F32_STATE, 0)
+    launch_of = np.zeros(n, dtype=np.int64) if launch_of is None else np.asarray(launch_of, dtype=np.int64)
+    assert n > 0 and bool((launch_of[1:] >= launch_of[:-1]).all())
+    bounds = [0] + [int(i) + 1 for i in np.flatnonzero(launch_of[1:] != launch_of[:-1])] + [n]
+    launches = []
+    for start, end in zip(bounds[:-1], bounds[1:]):
+        host["work0"][start:end], work = work_blocks(host["n"][start:end], QBLOCK)
+        launches.append((start, end, work))
+    return host, launches
+
+
+def adamw_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, rows=None):
+    """The ``t2v_adamw_tensor`` records of the tensors, in order -> (numpy record array, launches).  ``rows``: the hyper row of every
+    tensor, non-decreasing (None: all 0).  A launch takes at most ``MAX_HYPER`` distinct rows: ``launches`` is a list of
+    ``(first record, end record, work blocks, first row, rows)``; ``work0`` counts from the launch's first record and ``hyper`` from
+    its first row.  Gradients only (``t2v_sumsq_multi`` / ``t2v_scale_multi`` read nothing else): leave the other lists out."""
+    n = len(grads)
+    host = np.zeros(n, dtype=record_dtype(nt.AdamwTensor))
+    host["grad"], host["n"] = _ptrs(grads), _numels(grads)
+    for field, lst in (("param", params), ("exp_avg", exp_avgs), ("exp_avg_sq", exp_avg_sqs)):
+        if lst is not None:
+            host[field] = _ptrs(lst)
+    rows = np.zeros(n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+    assert n > 0 and bool((host["n"] > 0).all()) and bool((rows[1:] >= rows[:-1]).all())
+    launches, start = [], 0
+    while start < n:
+        end = int(np.searchsorted(rows, rows[start] + MAX_HYPER, side="left"))
+        host["work0"][start:end], work = work_blocks(host["n"][start:end], nt.ADAMW_BLOCK)
+        host["hyper"][start:end] = rows[start:end] - rows[start]
+        launches.append((start, end, work, int(rows[start]), int(rows[end - 1] - rows[start]) + 1))
+        start = end
+    return host, launches
+
+
+def upload(host, dev, out=None):
+    """A record array -> uint8 tensor on ``dev`` (``out``, if given: the table it replaces, of the same size); to a GPU through pinned
+    memory, so that the host never waits.  Returns (device tensor, what has to stay alive while the copy may still be reading it)."""
+    src = torch.from_numpy(host.view(np.uint8))
+    if dev.type != "cuda":
+        return (src.clone() if out is None else out.copy_(src)), None
+    pinned = src.pin_memory()
+    table = torch.empty(host.nbytes, dtype=torch.uint8, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        table.copy_(pinned, non_blocking=True)
+    return table, pinned
+
+
+class _Recent(dict):
+    """The plans of the few most recently used keys, most recently used last."""
+    capacity = 4
+
+    def lookup(self, key, build):
+        """The plan of ``key``, made by ``build()`` if it is not here; a ``build()`` that returns None leaves nothing behind."""
+        plan = self.pop(key, None)
+        if plan is None:
+            plan = build()
+        if plan is not None:
+            self[key] = plan
+            while len(self) > self.capacity:
+                del self[next(iter(self))]
+        return plan
+
+
+def touch(tensors):
+    """The kernels write through raw pointers, behind torch's back: move the version counters of ``tensors`` — no launch — so that
+    ``packs.params_fingerprint`` changes and the engines that packed these weights re-fill their packs instead of running on the old ones."""
+    torch.autograd.graph.increment_version(tensors)
 
 
 class FlatAdamW:
@@ -42,7 +155,7 @@ class FlatAdamW:
 
     def _hip(self):
         if self._ops is None:
-            self._ops = _shared_ops()
+            self._ops = shared_ops()
             self._ws = torch.empty(1025, dtype=torch.float32, device=self.flat_param.device)
         return self._ops
 
@@ -75,11 +188,9 @@ class FlatAdamW:
             self.exp_avg_sq.mul_(b2).addcmul_(gr, gr, value=1 - b2)
             bc1, bc2 = 1 - b1 ** self.step_count, 1 - b2 ** self.step_count
             self.flat_param.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / bc2 ** 0.5 + self.eps, value=-self.lr / bc1)
-        # The parameters are views of flat_param through ``.data``: neither the fused kernel nor an in-place op on the flat
-        # buffer moves THEIR version counters, and the native engines key their packed (LoRA-merged) weights on those
-        # (engine.params_fingerprint).  Touch one parameter so that a later inference call re-packs instead of sampling with
-        # the weights of the previous step.
-        self.params[0].add_(0.0)
+        # The parameters are ``.data`` views of flat_param: neither the kernel nor an in-place op on the flat buffer moves THEIR
+        # version counters, which the engines key their packed (LoRA-merged) weights on.
+        touch(self.params[0])
         for hook in self.after_step_hooks:   # e.g. UNetGradEngine.invalidate_lora_packs (engine_lora.py)
             hook()
         return norm
@@ -88,50 +199,21 @@ class FlatAdamW:
         self.sync.zero_()
 
 
-_OPS = None
-
-
-def _shared_ops():
-    """One ``HipOps`` per process for the flat-buffer kernels (its constructor parses the GEMM tune table)."""
-    global _OPS
-    if _OPS is None:
-        from .native import HipOps
-        _OPS = HipOps()
-    return _OPS
-
-
 @torch.no_grad()
 def update_ema_flat(target_flat, source_flat, rate=0.99, target_params=None):
     """EMA of a flat fp32 parameter buffer (utils/common_utils.py:307-319) in one kernel.  ``target_params``: the target
     network's parameters if they are ``.data`` views of ``target_flat`` — one of their version counters is moved so that the
     native engines re-pack the target's weights (see FlatAdamW.step)."""
     if target_flat.is_cuda:
-        _shared_ops().ema_update(target_flat, source_flat, rate)
+        shared_ops().ema_update(target_flat, source_flat, rate)
     else:
         target_flat.mul_(rate).add_(source_flat, alpha=1 - rate)
     if target_params:
-        target_params[0].add_(0.0)
+        touch(target_params[0])
 
 
 # ------------------------------------------------------------------------------------------------ EMA of a module tree
-_EMA_DTYPE = np.dtype([("target", "<u8"), ("src", "<u8"), ("n", "<i8"), ("work0", "<i8"), ("src_dt", "<i4"), ("reserved", "<i4")])  # struct t2v_ema_tensor
-_EMA_TABLES = {}      # key -> cached device table (the few most recently used: a target / student pair keeps one)
-_EMA_TABLES_MAX = 4
-
-
-def ema_table(targets, sources):
-    """The ``t2v_ema_tensor`` records of the pairs, in order -> (numpy record array, work blocks of the launch)."""
-    from .native import BF16, EMA_BLOCK, F32
-    host = np.zeros(len(targets), dtype=_EMA_DTYPE)
-    work = 0
-    for i, (t, s) in enumerate(zip(targets, sources)):
-        host[i] = (t.data_ptr(), s.data_ptr(), t.numel(), work, BF16 if s.dtype == torch.bfloat16 else F32, 0)
-        work += (t.numel() + EMA_BLOCK - 1) // EMA_BLOCK
-    return host, work
-
-
-_T = torch.Tensor
-_dtype_of, _is_cuda = operator.attrgetter("dtype"), operator.attrgetter("is_cuda")
+_EMA_TABLES = _Recent()      # key -> cached device table (a target / student pair keeps one)
 
 
 def _ema_key(targets, sources):
@@ -144,8 +226,7 @@ def _ema_key(targets, sources):
 
 def _ema_plan(targets, sources):
     """Sort the pairs — the ones ONE t2v_ema_multi launch takes (fp32 contiguous target, fp32 / bf16 contiguous source of the same size,
-    all on one GPU) and the rest — and put the launch's descriptor table on the device.  It goes up through pinned memory, so the host
-    never waits for it, and stays there until a tensor of either list is re-homed, resized or cast (``_ema_key``)."""
+    all on one GPU) and the rest — and ``upload`` the launch's table, kept until a tensor is re-homed, resized or cast (``_ema_key``)."""
     native, rest, dev = [], [], None
     for i, (t, s) in enumerate(zip(targets, sources)):
         ok = (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and s.device == t.device and s.is_contiguous()
@@ -157,10 +238,7 @@ def _ema_plan(targets, sources):
     plan = dict(native=native, rest=rest, dev=dev)
     if native:
         host, work = ema_table([targets[i] for i in native], [sources[i] for i in native])
-        pinned = torch.from_numpy(host.view(np.uint8)).pin_memory()
-        table = torch.empty(host.nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            table.copy_(pinned, non_blocking=True)
+        table, pinned = upload(host, dev)
         plan.update(table=table, pinned=pinned, work=work)   # (``pinned`` is kept: the copy may still be reading it)
     return plan
 
@@ -178,27 +256,17 @@ def update_ema(target_params, source_params, rate=0.99):
         for t, s in zip(targets, sources):
             t.detach().mul_(rate).add_(s.to(t.dtype), alpha=1 - rate)
         return
-    key = _ema_key(targets, sources)
-    plan = _EMA_TABLES.pop(key, None)
-    if plan is None:
-        plan = _ema_plan(targets, sources)
-    _EMA_TABLES[key] = plan                      # most recently used last
-    while len(_EMA_TABLES) > _EMA_TABLES_MAX:
-        _EMA_TABLES.pop(next(iter(_EMA_TABLES)))
+    plan = _EMA_TABLES.lookup(_ema_key(targets, sources), lambda: _ema_plan(targets, sources))
     for i in plan["rest"]:
         t, s = targets[i], sources[i]
         t.detach().mul_(rate).add_(s.to(t.dtype), alpha=1 - rate)
     if plan["native"]:
         with torch.cuda.device(plan["dev"]):
-            _shared_ops().ema_multi(plan["table"], len(plan["native"]), plan["work"], float(rate))
-        # The kernel writes through raw pointers: move one version counter so that the engines that packed the target's weights see
-        # the update (engine.params_fingerprints) and re-fill their packs, as FlatAdamW.step and update_ema_flat do.
-        targets[plan["native"][0]].detach().add_(0.0)
+            shared_ops().ema_multi(plan["table"], len(plan["native"]), plan["work"], float(rate))
+        touch(targets[plan["native"][0]])
 
 
 # ------------------------------------------------------------------------------------------------ block-wise 8-bit AdamW
-QBLOCK = 256  # elements per quantisation block (T2V_ADAMW8_BLOCK)
-
 
 def _dynamic_levels(top, decades):
     """Values in (0, 1), denser toward 0: decade d = 0, 1, ... covers [10^-(d+1), 10^-d] with ``top >> d`` evenly spaced values
@@ -240,7 +308,7 @@ def quantize_blockwise(x, code):
     if x.is_cuda:
         codes = torch.empty(nb * QBLOCK, dtype=torch.uint8, device=x.device)
         absmax = torch.empty(nb, dtype=torch.float32, device=x.device)
-        _shared_ops().quant8(x.contiguous(), code.to(x.device), codes, absmax)
+        shared_ops().quant8(x.contiguous(), code.to(x.device), codes, absmax)
         return codes, absmax
     xp = torch.zeros(nb * QBLOCK, dtype=torch.float32)
     xp[:n] = x
@@ -255,7 +323,7 @@ def dequantize_blockwise(codes, absmax, code, n):
     """The inverse map: value = code[byte] * absmax[block], the first ``n`` elements."""
     if codes.is_cuda:
         out = torch.empty(n, dtype=torch.float32, device=codes.device)
-        _shared_ops().dequant8(codes, absmax, code.to(codes.device), out)
+        shared_ops().dequant8(codes, absmax, code.to(codes.device), out)
         return out
     nb = (n + QBLOCK - 1) // QBLOCK
     return (code[codes[:nb * QBLOCK].long()].view(nb, QBLOCK) * absmax[:nb, None]).reshape(-1)[:n]
@@ -276,10 +344,6 @@ def adamw_definition(pf, grad, m, v, lr, betas, eps, wd, step, scale):
     v = v * float(b2) + (gr * float(f32(1) - b2)) * gr
     pf.sub_((m * float(step_size)) / (v.sqrt() / float(bc2_sqrt) + float(eps)))
     return m, v
-
-
-_TABLE_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state_block", "<i8"), ("n", "<i8"), ("work0", "<i8"),
-                         ("lr", "<f4"), ("weight_decay", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])   # struct t2v_adamw8_tensor
 
 
 class AdamW8bit(torch.optim.Optimizer):
@@ -378,15 +442,16 @@ class AdamW8bit(torch.optim.Optimizer):
         if step is not None:
             st["step"] = int(step)
         m, v = exp_avg.detach().to(p.device, torch.float32).reshape(-1), exp_avg_sq.detach().to(p.device, torch.float32).reshape(-1)
-        if not is8:
-            st["state1"].copy_(m)
-            st["state2"].copy_(v)
-            return
-        c1, c2 = self._codes_on(p.device)
-        for key, amk, x, code in (("state1", "absmax1", m, c1), ("state2", "absmax2", v, c2)):
-            codes, absmax = quantize_blockwise(x, code)
-            st[key].copy_(codes)
-            st[amk].copy_(absmax)
+        self._store(st, is8, m, v, *self._codes_on(p.device))
+
+    @staticmethod
+    def _store(st, is8, m, v, code1, code2):
+        """Fresh fp32 moments into a parameter's state: quantised block by block, or as they are where the state is fp32."""
+        for key, amk, x, code in (("state1", "absmax1", m, code1), ("state2", "absmax2", v, code2)):
+            if is8:
+                x, absmax = quantize_blockwise(x, code)
+                st[amk].copy_(absmax)
+            st[key].copy_(x)
 
     # -- the step ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -415,9 +480,7 @@ class AdamW8bit(torch.optim.Optimizer):
             for gi, p in active:
                 g = self.param_groups[gi]
                 self._step_cpu(p, g["lr"], g["betas"], g["eps"], g["weight_decay"], float(grad_scale))
-        # The kernel writes the parameters behind torch's back: move one version counter so that engine.params_fingerprint changes
-        # and the native engines re-pack their weights (as FlatAdamW.step does).
-        active[0][1].add_(0.0)
+        touch(active[0][1])
         return loss
 
     def _step_cpu(self, p, lr, betas, eps, wd, scale):
@@ -432,14 +495,7 @@ class AdamW8bit(torch.optim.Optimizer):
         else:
             m, v = st["state1"], st["state2"]
         m, v = adamw_definition(p.view(-1), p.grad.reshape(-1), m, v, lr, betas, eps, wd, step, scale)
-        if is8:
-            for key, amk, x, code in (("state1", "absmax1", m, self.code1), ("state2", "absmax2", v, self.code2)):
-                codes, absmax = quantize_blockwise(x, code)
-                st[key].copy_(codes)
-                st[amk].copy_(absmax)
-        else:
-            st["state1"].copy_(m)
-            st["state2"].copy_(v)
+        self._store(st, is8, m, v, self.code1, self.code2)
 
     def _step_hip(self, active, grad_scale):
         groups = self.param_groups
@@ -449,35 +505,27 @@ class AdamW8bit(torch.optim.Optimizer):
         sig = tuple((p.data_ptr(), p.grad.data_ptr(), k) for (gi, p), k in zip(active, keys))
         if self._table is None or self._table["sig"] != sig:
             order = sorted(range(len(active)), key=lambda i: keys[i])   # stable: parameters keep their order inside a launch
-            host = np.zeros(len(active), dtype=_TABLE_DTYPE)
-            launches, work, start = [], 0, 0
-            for j, i in enumerate(order):
-                gi, p = active[i]
-                if j > 0 and keys[i] != keys[order[j - 1]]:
-                    launches.append((start, j, work, keys[order[j - 1]]))
-                    start, work = j, 0
-                is8, b0, nb = self._layout[p]
-                host[j] = (p.data_ptr(), p.grad.data_ptr(), b0, p.numel(), work, 0.0, 0.0, 0 if is8 else 1, 0)
-                work += nb
-            launches.append((start, len(order), work, keys[order[-1]]))
-            dev = active[0][1].device
-            self._table = dict(sig=sig, host=host, launches=launches, group=np.array([active[i][0] for i in order]),
-                               dev=torch.empty(host.nbytes, dtype=torch.uint8, device=dev), uploaded=None)
+            ps = [active[i][1] for i in order]
+            layout = [self._layout[p] for p in ps]
+            launch_of = np.cumsum([j > 0 and keys[i] != keys[order[j - 1]] for j, i in enumerate(order)])
+            host, launches = adamw8_table(ps, [p.grad for p in ps], [b0 for _, b0, _ in layout], [not is8 for is8, _, _ in layout],
+                                          launch_of=launch_of)
+            self._table = dict(sig=sig, host=host, launches=[(s, e, work, keys[order[s]]) for s, e, work in launches],
+                               group=np.array([active[i][0] for i in order]), dev=None, pinned=None, uploaded=None)
         t = self._table
         t["host"]["lr"] = np.array([g["lr"] for g in groups], dtype=np.float32)[t["group"]]
         t["host"]["weight_decay"] = np.array([g["weight_decay"] for g in groups], dtype=np.float32)[t["group"]]
         image = t["host"].tobytes()
-        if t["uploaded"] != image:   # lr moves every scheduler step: 56 bytes per tensor
-            t["dev"].copy_(torch.frombuffer(bytearray(image), dtype=torch.uint8))
+        if t["uploaded"] != image:   # lr moves every scheduler step: 56 bytes per tensor, into the table that is there
+            t["dev"], t["pinned"] = upload(t["host"], active[0][1].device, out=t["dev"])   # (``pinned`` is kept: the copy may still be reading it)
             t["uploaded"] = image
         a = self._arena
         c1, c2 = self._codes_on(t["dev"].device)
-        ops = self.native_ops if self.native_ops is not None else _shared_ops()
+        ops = self.native_ops if self.native_ops is not None else shared_ops()
         opt = lambda x: x if x.numel() else None
-        import contextlib
         with torch.cuda.device(t["dev"].device) if t["dev"].is_cuda else contextlib.nullcontext():
             for start, end, work, (b1, b2, eps, dstep) in t["launches"]:
-                ops.adamw8_step(t["dev"][start * _TABLE_DTYPE.itemsize:], end - start, work, opt(a["s1"]), opt(a["s2"]), opt(a["a1"]),
+                ops.adamw8_step(t["dev"][start * t["host"].itemsize:], end - start, work, opt(a["s1"]), opt(a["s2"]), opt(a["a1"]),
                                 opt(a["a2"]), opt(a["f1"]), opt(a["f2"]), c1, c2, b1, b2, eps, step0 + dstep, grad_scale)
 
     # -- checkpoints ---------------------------------------------------------------------------------------------------------
@@ -516,55 +564,6 @@ class AdamW8bit(torch.optim.Optimizer):
 
 
 # ------------------------------------------------------------------------------------------------ fp32 AdamW and clipping, in place
-_ADAMW_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i8"), ("work0", "<i8"),
-                         ("hyper", "<i4"), ("reserved", "<i4")])   # struct t2v_adamw_tensor
-MAX_HYPER = 16   # T2V_ADAMW_MAX_HYPER
-
-
-def _ptrs(tensors):
-    return np.fromiter(map(_T.data_ptr, tensors), dtype=np.uint64, count=len(tensors))
-
-
-def adamw_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, rows=None):
-    """The ``t2v_adamw_tensor`` records of the tensors, in order -> (numpy record array, launches).  ``rows``: the hyper row of every
-    tensor, non-decreasing (None: all 0).  A launch takes at most ``MAX_HYPER`` distinct rows: ``launches`` is a list of
-    ``(first record, end record, work blocks, first row, rows)``; ``work0`` counts from the launch's first record and ``hyper`` from
-    its first row.  Gradients only (``t2v_sumsq_multi`` / ``t2v_scale_multi`` read nothing else): leave the other lists out."""
-    from .native import ADAMW_BLOCK
-    n = len(grads)
-    host = np.zeros(n, dtype=_ADAMW_DTYPE)
-    host["grad"] = _ptrs(grads)
-    for field, lst in (("param", params), ("exp_avg", exp_avgs), ("exp_avg_sq", exp_avg_sqs)):
-        if lst is not None:
-            host[field] = _ptrs(lst)
-    numel = np.fromiter(map(_T.numel, grads), dtype=np.int64, count=n)
-    blocks = (numel + ADAMW_BLOCK - 1) // ADAMW_BLOCK
-    rows = np.zeros(n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
-    assert n > 0 and bool((numel > 0).all()) and bool((rows[1:] >= rows[:-1]).all())
-    host["n"] = numel
-    launches, start = [], 0
-    while start < n:
-        end = int(np.searchsorted(rows, rows[start] + MAX_HYPER, side="left"))
-        host["work0"][start:end] = np.cumsum(blocks[start:end]) - blocks[start:end]
-        host["hyper"][start:end] = rows[start:end] - rows[start]
-        launches.append((start, end, int(blocks[start:end].sum()), int(rows[start]), int(rows[end - 1] - rows[start]) + 1))
-        start = end
-    return host, launches
-
-
-def _upload(host, dev):
-    """A record array -> uint8 tensor on ``dev``; to a GPU through pinned memory, so that the host never waits for the copy.  Returns
-    (device tensor, what has to stay alive while the copy may still be reading it)."""
-    src = torch.from_numpy(host.view(np.uint8))
-    if dev.type != "cuda":
-        return src.clone(), None
-    pinned = src.pin_memory()
-    table = torch.empty(host.nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        table.copy_(pinned, non_blocking=True)
-    return table, pinned
-
-
 def _check_dense_f32(what, tensors, dev):
     for t in tensors:
         if t.is_sparse or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
@@ -661,24 +660,18 @@ class AdamW(torch.optim.Optimizer):
         scale, scale_dev = (1.0, grad_scale.detach()) if torch.is_tensor(grad_scale) else (float(grad_scale), None)
         if scale_dev is not None and (scale_dev.device != dev or scale_dev.dtype != torch.float32 or scale_dev.numel() != 1):
             raise ValueError("AdamW.step: a tensor grad_scale must be one fp32 element on the parameters' device")
-        ops = self.native_ops if self.native_ops is not None else _shared_ops()
-        import contextlib
-        from .native import AdamwHyper
+        ops = self.native_ops if self.native_ops is not None else shared_ops()
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             for start, end, work, row0, n_rows in plan["launches"]:
-                hyper = (AdamwHyper * n_rows)(*[AdamwHyper(*r) for r in rows[row0:row0 + n_rows]])
-                ops.adamw_multi(plan["table"][start * _ADAMW_DTYPE.itemsize:], end - start, work, hyper, scale, scale_dev)
-        # The kernel writes the parameters behind torch's back: move every updated parameter's version counter — no launch — so that
-        # engine.params_fingerprint changes whichever module a parameter belongs to and the native engines re-pack their weights.
-        torch.autograd.graph.increment_version(active)
+                hyper = (nt.AdamwHyper * n_rows)(*[nt.AdamwHyper(*r) for r in rows[row0:row0 + n_rows]])
+                ops.adamw_multi(plan["table"][start * nt.C.sizeof(nt.AdamwTensor):], end - start, work, hyper, scale, scale_dev)
+        touch(active)   # every updated parameter: the fingerprint changes whichever module a parameter belongs to
         return loss
 
     def _make_plan(self, active, grads, states, ms, vs, key, dev):
         """Sort the tensors by hyper row — one row per (group, step) among them — and put the descriptor table on the device."""
-        _check_dense_f32("AdamW", active, dev)
-        _check_dense_f32("AdamW", grads, dev)
-        _check_dense_f32("AdamW", ms, dev)
-        _check_dense_f32("AdamW", vs, dev)
+        for lst in (active, grads, ms, vs):
+            _check_dense_f32("AdamW", lst, dev)
         group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
         # The step counts of the plan's tensors move into ONE fp32 CPU buffer and every state[p]["step"] becomes a 0-d view of it (still
         # torch's layout: a 0-d fp32 CPU tensor per parameter): a step then advances all of them with one add instead of one per tensor.
@@ -692,7 +685,7 @@ class AdamW(torch.optim.Optimizer):
         order = sorted(range(len(active)), key=lambda i: index[row_keys[i]])   # stable: parameters keep their order inside a row
         pick = lambda lst: [lst[i] for i in order]   # noqa: E731
         host, launches = adamw_table(pick(grads), pick(active), pick(ms), pick(vs), [index[row_keys[i]] for i in order])
-        table, pinned = _upload(host, dev)
+        table, pinned = upload(host, dev)
         self.table_uploads += 1
         return dict(key=key, table=table, pinned=pinned, launches=launches, rows=uniq, steps=step_buf, first_step=steps[0], uses=0)
 
@@ -713,8 +706,7 @@ class AdamW(torch.optim.Optimizer):
                 s["exp_avg_sq"].view(-1).copy_(v)
 
 
-_CLIP_PLANS = {}      # key -> cached device table and workspace (the few most recently used)
-_CLIP_PLANS_MAX = 4
+_CLIP_PLANS = _Recent()      # key -> cached device table and workspace
 
 
 def _clip_plan(parameters):
@@ -725,25 +717,23 @@ def _clip_plan(parameters):
     if not grads or not all(map(_is_cuda, grads)):
         return None, params
     key = (tuple(map(_T.data_ptr, grads)), tuple(map(_T.numel, grads)), tuple(map(_dtype_of, grads)), tuple(map(_T.is_contiguous, grads)))
-    plan = _CLIP_PLANS.pop(key, None)
-    if plan is None:
+
+    def build():
         dev = grads[0].device
         if any(g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or g.numel() == 0 for g in grads):
-            return None, params
+            return None
         host, launches = adamw_table(grads)
         (_, n, work, _, _), = launches
-        table, pinned = _upload(host, dev)
-        plan = dict(table=table, pinned=pinned, n=n, work=work, dev=dev, ws=torch.empty(work, dtype=torch.float32, device=dev))
-    _CLIP_PLANS[key] = plan                      # most recently used last
-    while len(_CLIP_PLANS) > _CLIP_PLANS_MAX:
-        _CLIP_PLANS.pop(next(iter(_CLIP_PLANS)))
-    return plan, params
+        table, pinned = upload(host, dev)
+        return dict(table=table, pinned=pinned, n=n, work=work, dev=dev, ws=torch.empty(work, dtype=torch.float32, device=dev))
+
+    return _CLIP_PLANS.lookup(key, build), params
 
 
 def _norm_and_coef(plan, max_norm):
     out = torch.empty(2, dtype=torch.float32, device=plan["dev"])   # a buffer of its own: what is returned outlives the next call
     with torch.cuda.device(plan["dev"]):
-        _shared_ops().sumsq_multi(plan["table"], plan["n"], plan["work"], plan["ws"], float(max_norm), out)
+        shared_ops().sumsq_multi(plan["table"], plan["n"], plan["work"], plan["ws"], float(max_norm), out)
     return out
 
 
@@ -762,7 +752,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
                            "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
                            "`error_if_nonfinite=False`")
     with torch.cuda.device(plan["dev"]):
-        _shared_ops().scale_multi(plan["table"], plan["n"], plan["work"], out[1:])
+        shared_ops().scale_multi(plan["table"], plan["n"], plan["work"], out[1:])
     return out[0]
 
 

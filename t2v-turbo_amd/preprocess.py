@@ -20,6 +20,7 @@ import torch
 
 from . import cd_head, motion_prior
 from .latent_io import pack_latent_record
+from .native import shared_ops
 
 RECORD_TENSORS = ("z_t", "cond_teacher_out", "uncond_teacher_out", "score", "z_example", "z_example_prev", "prompt_emb")
 
@@ -262,9 +263,8 @@ def make_latent_records(unet, solver, noise_scheduler, latents, prompt_embeds, u
         unet.native_input_grad = True          # the score's differentiated pass on the data-gradient engine
     try:
         if native:
-            from .optim import _shared_ops
             with torch.cuda.device(latents.device):
-                tensors, info = _make_native(_shared_ops(), unet, solver, noise_scheduler, latents, prompt_embeds, uncond_prompt_embeds,
+                tensors, info = _make_native(shared_ops(), unet, solver, noise_scheduler, latents, prompt_embeds, uncond_prompt_embeds,
                                              index, noise, motion, fps, temp_loss_scale)
         else:
             tensors, info = _make_torch(unet, solver, noise_scheduler, latents, prompt_embeds, uncond_prompt_embeds, index, noise, motion,

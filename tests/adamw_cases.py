@@ -174,7 +174,7 @@ class AdamwCase:
 def adamw8_f32_state(ops, case, snap, grad_scale):
     """{tensor: (param, exp_avg, exp_avg_sq)} after ``t2v_adamw8_step`` on COPIES of the snapshot's data, every tensor under
     T2V_ADAMW8_F32_STATE (fp32 moments in an arena padded to whole 256-element blocks), one launch per hyper row."""
-    from t2v_turbo_amd.optim import QBLOCK, _TABLE_DTYPE, make_code_books
+    from t2v_turbo_amd.optim import QBLOCK, adamw8_table, make_code_books, work_blocks
     dev = case.arena["p"].device
     code1, code2 = (c.to(dev) for c in make_code_books())
     got = {}
@@ -182,23 +182,18 @@ def adamw8_f32_state(ops, case, snap, grad_scale):
         idx = [i for i in case.active if GROUP_OF[i] == row]
         p = [case._span(snap, "p", i).clone() for i in idx]
         g = [case._span(snap, "g", i).clone() for i in idx]
-        blocks = [(CASES[i][0] + QBLOCK - 1) // QBLOCK for i in idx]
-        f1, f2 = torch.zeros(sum(blocks) * QBLOCK, device=dev), torch.zeros(sum(blocks) * QBLOCK, device=dev)
-        host = np.zeros(len(idx), dtype=_TABLE_DTYPE)
-        b0 = 0
-        for j, i in enumerate(idx):
-            n = CASES[i][0]
-            f1[b0 * QBLOCK:b0 * QBLOCK + n] = case._span(snap, "m", i)
-            f2[b0 * QBLOCK:b0 * QBLOCK + n] = case._span(snap, "v", i)
-            host[j] = (p[j].data_ptr(), g[j].data_ptr(), b0, n, b0, h[0], h[1], nt.ADAMW8_F32_STATE, 0)
-            b0 += blocks[j]
+        first, total = work_blocks([CASES[i][0] for i in idx], QBLOCK)   # every tensor's first block in the state arena: its work0 too
+        f1, f2 = torch.zeros(total * QBLOCK, device=dev), torch.zeros(total * QBLOCK, device=dev)
+        spans = [slice(int(b0) * QBLOCK, int(b0) * QBLOCK + CASES[i][0]) for b0, i in zip(first, idx)]
+        for sp, i in zip(spans, idx):
+            f1[sp] = case._span(snap, "m", i)
+            f2[sp] = case._span(snap, "v", i)
+        host, ((_, _, work),) = adamw8_table(p, g, first, True, lr=h[0], weight_decay=h[1])
+        assert work == total and np.array_equal(host["work0"], first)
         table = torch.from_numpy(host.view(np.uint8).copy()).to(dev)
-        ops.adamw8_step(table, len(idx), b0, None, None, None, None, f1, f2, code1, code2, h[2], h[3], h[4], step0 + 1, grad_scale)
-        b0 = 0
-        for j, i in enumerate(idx):
-            n = CASES[i][0]
-            got[i] = (p[j], f1[b0 * QBLOCK:b0 * QBLOCK + n].clone(), f2[b0 * QBLOCK:b0 * QBLOCK + n].clone())
-            b0 += blocks[j]
+        ops.adamw8_step(table, len(idx), work, None, None, None, None, f1, f2, code1, code2, h[2], h[3], h[4], step0 + 1, grad_scale)
+        for sp, pj, i in zip(spans, p, idx):
+            got[i] = (pj, f1[sp].clone(), f2[sp].clone())
     return got
 
 

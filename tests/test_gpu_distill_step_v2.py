@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from t2v_turbo_amd import cd_head, cd_math, optim
+from t2v_turbo_amd import native as nt
 from t2v_turbo_amd.distill import distill_step_v2
 from t2v_turbo_amd.engine import UNetEngine
 from t2v_turbo_amd.scheduler import T2VTurboScheduler
@@ -41,7 +42,7 @@ def test_three_train_mode_steps_on_the_native_routes_with_the_native_head():
     target = copy.deepcopy(student).requires_grad_(False).train()
     opt = optim.AdamW8bit(student.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8)
     want = [p.detach().clone() for p in target.parameters()]
-    ops = optim._shared_ops()
+    ops = nt.shared_ops()
     calls = {"cd_solver_step": 0, "cd_loss_fwd": 0, "cd_loss_bwd": 0}
 
     def counted(name):

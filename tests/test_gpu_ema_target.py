@@ -45,7 +45,7 @@ def test_update_ema_is_one_launch_with_a_cached_table():
     holder = torch.nn.ParameterList(tg)
     want = [t.detach().clone() for t in tg]
     calls = []
-    ops = optim._shared_ops()
+    ops = nt.shared_ops()
     real = ops.ema_multi
     ops.ema_multi = lambda *a: (calls.append(a[1:3]), real(*a))[1]
     try:

@@ -92,8 +92,7 @@ def test_uint8_refusals(ops):
 
 # --------------------------------------------------------------------------------------------------------------- the sampler
 def shared_ops():
-    from t2v_turbo_amd.optim import _shared_ops
-    return _shared_ops()
+    return nt.shared_ops()
 
 
 @pytest.fixture(scope="module")

@@ -7,8 +7,8 @@ import warnings
 import pytest
 import torch
 
-from t2v_turbo_amd.optim import AdamW8bit
-from tests.optim8_util import build_case, compare_with_restatement, cpu_twin, random_state
+from t2v_turbo_amd.optim import QBLOCK, AdamW8bit
+from tests.optim8_util import RTOL, build_case, compare_with_restatement, cpu_twin, random_state, table_gap
 from tests.util import load, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +71,43 @@ def test_large_multi_tensor_launch():
     total, off = _check_steps(opt, 5, "large", 1.0, new_grads)
     assert total >= 2 * 32 * (1 << 20) * 5 * 0.99
     assert len(opt._table["launches"]) >= 2
+
+
+def test_table_goes_up_again_when_a_learning_rate_moves_into_the_same_device_table():
+    """The descriptor table's way to the device (pinned, asynchronous, into the table that is there): five tensors on both sides of
+    ``min_8bit_size`` in two groups, three steps, the second group's ``lr`` moved before step 2 and left alone before step 3.  Every
+    step against the restatement by ``compare_with_restatement``'s bounds — a stale table would step with the old ``lr``, far outside
+    them — and the dequantised moments with it: equal codes and bit-equal absmax give equal values, a code off by one at most one table
+    gap times the block's absmax (plus 3 * 2**-24 of the absmax: the two values and the gap are one rounded fp32 product each, none
+    larger than the absmax); the fp32 moments of the small tensors to fp32 rounding."""
+    gen = torch.Generator().manual_seed(11)
+    params = [torch.nn.Parameter((torch.randn(n, generator=gen) * 0.1).cuda()) for n in (1, 255, 4096, 4097, 10561)]
+    for p in params:
+        p.grad = (torch.randn(p.numel(), generator=gen) * 0.3).cuda()
+    opt = AdamW8bit([{"params": params[:3]}, {"params": params[3:], "lr": 3e-2}], lr=1e-2, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-2)
+    random_state(opt, params, gen)
+    tables, images = [], []
+    for s in range(3):
+        if s == 1:
+            opt.param_groups[1]["lr"] = 5e-3
+        twin, pairs = cpu_twin(opt)
+        opt.step()
+        torch.cuda.synchronize()
+        twin.step()
+        compare_with_restatement(opt, pairs, twin, f"table upload step {s + 1}")
+        for p, q in pairs:
+            for k, (a, b) in enumerate(zip(opt.moments(p), twin.moments(q))):
+                if "absmax1" in twin.state[q]:
+                    absmax = twin.state[q][f"absmax{k + 1}"].repeat_interleave(QBLOCK)[:q.numel()]
+                    gap = table_gap((twin.code1, twin.code2)[k]) + 3 * 2.0 ** -24
+                    assert bool(((a.cpu() - b).abs() <= gap * absmax).all()), (s, p.numel(), k)
+                else:
+                    assert torch.allclose(a.cpu(), b, rtol=RTOL, atol=1e-12), (s, p.numel(), k)
+        tables.append(opt._table["dev"].data_ptr())
+        images.append(opt._table["uploaded"])
+    assert len(set(tables)) == 1 and opt._table["dev"].is_cuda and opt._table["pinned"].is_pinned()
+    assert images[0] != images[1] and images[1] is images[2]          # one upload for the moved lr, none for the step after
+    assert bytes(opt._table["dev"].cpu().numpy().tobytes()) == images[2] and len(opt._table["launches"]) == 1
 
 
 def test_same_step_twice_from_the_same_state_is_bit_identical():

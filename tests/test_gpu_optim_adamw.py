@@ -9,7 +9,8 @@ import torch
 
 from t2v_turbo_amd import native as nt
 from t2v_turbo_amd import optim
-from t2v_turbo_amd.optim import AdamW, _shared_ops, clip_grad_norm_, grad_clip_coef
+from t2v_turbo_amd.native import shared_ops
+from t2v_turbo_amd.optim import AdamW, clip_grad_norm_, grad_clip_coef
 from tests.adamw_cases import (B, NO_GRAD, RTOL, ATOL, AdamwCase, bits, check_against_adamw8, check_twin, many_groups, norm_bound,
                                twin_step)
 from tests.util import load, rel_l2
@@ -21,7 +22,7 @@ pytestmark = pytest.mark.gpu
 def test_case_list_one_launch_against_adamw8_and_the_definition(host_scale, dev_scale):
     """The kernel called directly over the case table: bit-identical to the fp32-state branch of ``t2v_adamw8_step``, moments
     bit-equal to the torch definition, parameters within fp32 rounding, guards and gradients bit-unchanged."""
-    ops = _shared_ops()
+    ops = shared_ops()
     case = AdamwCase("cuda")
     snap = case.snapshot()
     table, n, work, hyper, order = case.table()
@@ -62,7 +63,7 @@ def test_more_than_16_hyper_rows_take_a_second_launch():
 
 
 def test_sumsq_and_scale_on_the_case_table():
-    ops = _shared_ops()
+    ops = shared_ops()
     case = AdamwCase("cuda", seed=8)
     table, n, work, _, order = case.table()
     want = sum(float((case.tensors(i)[1].double() ** 2).sum()) for i in order)

@@ -166,8 +166,7 @@ def produced():
 
 
 def preprocess_ops():
-    from t2v_turbo_amd.optim import _shared_ops
-    return _shared_ops()
+    return nt.shared_ops()
 
 
 def _stack(blobs):

@@ -37,7 +37,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_adamw8_step.json"))
     args = ap.parse_args()
     from bench import VC2_UNET
-    from t2v_turbo_amd.optim import AdamW8bit, _shared_ops
+    from t2v_turbo_amd.native import shared_ops
+    from t2v_turbo_amd.optim import AdamW8bit
     from t2v_turbo_amd.unet3d import UNetModel
     with torch.device("meta"):
         shapes = [tuple(p.shape) for p in UNetModel(**VC2_UNET).parameters()]
@@ -67,7 +68,7 @@ def main():
     r8 = rate(timed(lambda: opt.step(), args.reps), 16)
     t, a = opt._table, opt._arena
     c1, c2 = opt._codes_on(dev)
-    ops = _shared_ops()
+    ops = shared_ops()
     (start, end, work, _), = t["launches"]
     k8 = rate(timed(lambda: ops.adamw8_step(t["dev"], end - start, work, a["s1"], a["s2"], a["a1"], a["a2"], a["f1"], a["f2"], c1, c2,
                                             0.9, 0.999, 1e-8, 100, 1.0), args.reps), 16)

@@ -77,12 +77,13 @@ def interleaved(rows, reps, warmup=3):
 
 def bench_list(name, shapes, dev, reps):
     from t2v_turbo_amd import optim
-    from t2v_turbo_amd.optim import AdamW, AdamW8bit, _shared_ops, clip_grad_norm_, grad_clip_coef
+    from t2v_turbo_amd.native import shared_ops
+    from t2v_turbo_amd.optim import AdamW, AdamW8bit, clip_grad_norm_, grad_clip_coef
     gen = torch.Generator(device=dev).manual_seed(0)
     params, flat_p, flat_g = make_params(shapes, dev, gen)
     n_elem = sum(p.numel() for p in params)
     g0 = flat_g.clone()
-    ops = _shared_ops()
+    ops = shared_ops()
 
     ours = AdamW(params, **HYPER)
     ours.step()
